@@ -6,7 +6,11 @@ For N>1 the driver launches it under ``torch.distributed.run`` with one
 rank per GPU (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in env), RCCL over xGMI.
 W untimed warmup steps, then exactly K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX time over ranks;
-rank 0 prints ONE JSON line.
+rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` additionally writes
+what the last timed step computed as ``DIR/<name>.npy`` (same arguments =>
+same inputs, so two builds can be compared output for output).  ``--full``
+adds the instrumented per-phase steps behind the ``comm_breakdown`` field
+(``null`` in a plain run).
 
 Metric (BASELINE.json): examples/sec (whole node), Criteo wide-and-deep,
 synthetic Criteo-shaped data, random-init weights, bf16 compute, weak
@@ -20,6 +24,8 @@ import json
 import os
 import sys
 import time
+
+_T_START = time.perf_counter()  # log() stamps set-up phases against this
 
 # hipBLASLt algorithm tuning for the MLP GEMM shapes (must be set before
 # the first GEMM).  A pre-tuned table for the default config ships in
@@ -57,7 +63,46 @@ N_DATA_BATCHES = 8  # distinct synthetic batches cycled through
 
 
 def log(msg: str) -> None:
-    print(f"[bench] {msg}", file=sys.stderr, flush=True)
+    print(f"[bench +{time.perf_counter() - _T_START:.1f}s] {msg}",
+          file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE_ROWS = 131072  # embedding rows kept per table by --dump-outputs
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir: str, model: torch.nn.Module,
+                 last_loss: torch.Tensor, rank: int,
+                 world_size: int) -> None:
+    """Write what a caller of the timed step receives after its last call:
+    the returned loss and the updated model state, one float32
+    ``<name>.npy`` each.  Dense parameters are written whole; the sparse
+    tables (GBs at the default size) as a fixed seeded sample of rows, with
+    the sampled row numbers in ``<name>.rows.npy`` (float64).  Under
+    ``--gpus N`` every rank writes its own shard with a ``.rankR`` infix."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    infix = f".rank{rank}" if world_size > 1 else ""
+
+    def save(name: str, t: torch.Tensor, dtype=torch.float32) -> None:
+        arr = t.detach().to("cpu", dtype).contiguous().numpy()
+        np.save(os.path.join(out_dir, f"{name}{infix}.npy"), arr)
+
+    save("loss", last_loss.reshape(1))
+    for name, p in model.named_parameters():
+        if not getattr(p, "_miyarn_sparse", False):
+            save(name, p)
+            continue
+        n_rows = p.shape[0]
+        if n_rows > DUMP_SAMPLE_ROWS:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            rows = torch.from_numpy(np.unique(
+                rng.integers(0, n_rows, size=DUMP_SAMPLE_ROWS)))
+        else:
+            rows = torch.arange(n_rows)
+        save(name, p.detach().index_select(0, rows.to(p.device)))
+        save(f"{name}.rows", rows, torch.float64)
 
 
 def _ensure_master_port(rank: int) -> None:
@@ -116,9 +161,20 @@ def main() -> None:
     parser.add_argument("--table-rows", type=int,
                         default=TABLE_ROWS_PER_FEATURE,
                         help="rows per categorical table (tests use small)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run everything beyond the headline "
+                             "figure (the instrumented comm_breakdown "
+                             "steps); a plain run only sets up, warms up, "
+                             "times --steps steps and prints the result")
     parser.add_argument("--probe-steps", type=int, default=3,
-                        help="instrumented steps AFTER the timed region "
-                             "for the comm_breakdown JSON field (0=off)")
+                        help="with --full: instrumented steps AFTER the "
+                             "timed region for the comm_breakdown JSON "
+                             "field (0=off)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps write what the last "
+                             "timed step computed (loss, dense parameters, "
+                             "a fixed seeded sample of embedding rows) as "
+                             "DIR/<name>.npy in float32")
     parser.add_argument("--graphs", action="store_true",
                         help="capture the step in a hipGraph (measured "
                              "2.39 vs 2.10 ms/step eager on MI355X — "
@@ -144,6 +200,7 @@ def main() -> None:
     compute_dtype = (torch.bfloat16 if args.dtype == "bf16" and use_gpu
                      else torch.float32)
     table_sizes = [args.table_rows] * 26
+    log("imports done, building model")
 
     torch.manual_seed(1234 + rank)  # sharded tables are per-rank
     # Feature-sharded embeddings + all-to-all: the xGMI-native scaling
@@ -162,6 +219,7 @@ def main() -> None:
     opt = FusedSGD([p for p in model.parameters()
                     if not getattr(p, "_miyarn_sparse", False)], lr=lr)
 
+    log("model on device, generating batches")
     # Pre-generate distinct synthetic batches on-device (data=synthetic;
     # varying ids each step so the gather/scatter path is exercised).
     batches = []
@@ -229,6 +287,7 @@ def main() -> None:
         torch.cuda.synchronize()
     if world_size > 1:
         dist.barrier()
+    log("warmup done, timing")
     t0 = time.perf_counter()
     last_loss = None
     for i in range(args.steps):
@@ -250,12 +309,18 @@ def main() -> None:
         / args.steps * 1000.0
     elapsed = float(t.item())
 
-    # -- per-phase comm/compute breakdown (extra instrumented steps AFTER
-    # the timed region; headline number is unperturbed).  Makes a poor
-    # scaling curve attributable: alltoall ids/vec/wide/grad, wide
+    # before the --full probe steps below train the model any further
+    if args.dump_outputs and last_loss is not None:
+        dump_outputs(args.dump_outputs, model, last_loss, rank, world_size)
+        log(f"rank {rank}: outputs of the last timed step written to "
+            f"{args.dump_outputs}")
+
+    # -- per-phase comm/compute breakdown (--full only: extra instrumented
+    # steps AFTER the timed region; headline number is unperturbed).  Makes
+    # a poor scaling curve attributable: alltoall ids/vec/wide/grad, wide
     # allgather, dense-reducer drain, plus fwd/bwd/opt phase times.
     breakdown = None
-    if args.probe_steps > 0:
+    if args.full and args.probe_steps > 0:
         from tf_yarn_amd.utils import commprobe
         commprobe.reset()
         commprobe.enable()

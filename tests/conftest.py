@@ -16,6 +16,20 @@ def pytest_collection_modifyitems(config, items):
     pass
 
 
+@pytest.fixture(autouse=True, scope="session")
+def _app_base_dir(tmp_path_factory):
+    """Launched applications keep their working dirs under pytest's own
+    temp dir (the launcher's default is a fixed, shared directory that
+    another user's earlier run may own)."""
+    if "MIYARN_APP_BASE_DIR" in os.environ:
+        yield
+        return
+    os.environ["MIYARN_APP_BASE_DIR"] = str(
+        tmp_path_factory.mktemp("miyarn_apps"))
+    yield
+    del os.environ["MIYARN_APP_BASE_DIR"]
+
+
 @pytest.fixture
 def kv_server():
     from tf_yarn_amd.kv import KVServer

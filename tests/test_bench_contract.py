@@ -50,10 +50,54 @@ def _check_json_line(stdout: str, n_gpus: int):
 def test_bench_single_process():
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
-         "--batch", "64", "--table-rows", "1000", "--dtype", "fp32"],
+         "--batch", "64", "--table-rows", "1000", "--dtype", "fp32",
+         "--full"],
         cwd=REPO, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
-    _check_json_line(out.stdout, 1)
+    result = _check_json_line(out.stdout, 1)
+    assert result["comm_breakdown"]["phase_forward"]["calls_per_step"] == 1
+
+
+def _plain_run_with_dump(dump_dir):
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+         "--warmup", "1", "--batch", "64", "--table-rows", "1000",
+         "--dtype", "fp32", "--dump-outputs", str(dump_dir)],
+        cwd=REPO, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return _check_json_line(out.stdout, 1)
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run skips the --full extras, really runs --steps timed
+    steps, and --dump-outputs writes the last step's loss + model state
+    as float32 .npy files that a second identical run reproduces."""
+    import numpy as np
+
+    result = _plain_run_with_dump(tmp_path / "a")
+    assert result["comm_breakdown"] is None
+    assert result["steps"] == 3
+    _plain_run_with_dump(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    for expected in ("loss.npy", "embeddings.weight.npy",
+                     "embeddings.wide_weight.npy", "mlp.0.weight.npy",
+                     "head.weight.npy"):
+        assert expected in names
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.isfinite(a).all(), name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,)
+    assert float(loss[0]) == pytest.approx(result["config"]["final_loss"],
+                                           rel=1e-6)
 
 
 @pytest.mark.timeout(300)
@@ -64,7 +108,7 @@ def test_bench_under_torchrun_2_ranks():
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", _free_port(), "bench.py", "--gpus", "2",
          "--steps", "2", "--warmup", "1", "--batch", "64",
-         "--table-rows", "1000", "--dtype", "fp32"],
+         "--table-rows", "1000", "--dtype", "fp32", "--full"],
         cwd=REPO, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     _check_json_line(out.stdout, 2)
@@ -79,7 +123,7 @@ def test_bench_under_torchrun_4_ranks_uneven_shards():
          "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
          "--master-port", _free_port(), "bench.py", "--gpus", "4",
          "--steps", "2", "--warmup", "1", "--batch", "32",
-         "--table-rows", "500", "--dtype", "fp32"],
+         "--table-rows", "500", "--dtype", "fp32", "--full"],
         cwd=REPO, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     _check_json_line(out.stdout, 4)
@@ -94,7 +138,7 @@ def test_bench_under_torchrun_8_ranks():
          "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
          "--master-port", _free_port(), "bench.py", "--gpus", "8",
          "--steps", "2", "--warmup", "1", "--batch", "16",
-         "--table-rows", "200", "--dtype", "fp32"],
+         "--table-rows", "200", "--dtype", "fp32", "--full"],
         cwd=REPO, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     _check_json_line(out.stdout, 8)

@@ -198,7 +198,10 @@ def test_binned_wrappers_cpu_fallback():
 
 def test_bench_master_port_rank0_picks_free_port(tmp_path, monkeypatch):
     import socket
+    import tempfile
     import bench
+    # the rendezvous file lives in the temp dir: keep it in this test's own
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     monkeypatch.setenv("MIYARN_RDV_TAG", "utest")
     monkeypatch.delenv("MASTER_PORT", raising=False)
     # occupy 29500 so the fallback must move past it

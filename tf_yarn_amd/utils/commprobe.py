@@ -6,8 +6,8 @@ sparse allgathers, dense-reducer drain) records its device time via CUDA
 event pairs (host ``perf_counter`` on CPU/gloo), and ``summary()``
 reduces them to per-tag totals.  Disabled (the default) the probe is a
 zero-cost no-op, so the bench's headline timed region is unperturbed —
-bench.py runs a few *extra* instrumented steps after the timed region
-and emits the result as ``comm_breakdown`` in its JSON line.
+``bench.py --full`` runs a few *extra* instrumented steps after the timed
+region and emits the result as ``comm_breakdown`` in its JSON line.
 
 The reference delegates this diagnosis surface entirely to
 ``NCCL_DEBUG=INFO`` (``pytorch/tasks/worker.py:95``); here the per-phase
