@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Micro-benchmark of the sparse Adagrad apply at the bench shape
+(b=65536, 26 features x 1M rows, dim 16 deep + dim 1 wide, bf16 grads).
+
+Timed, on identical inputs:
+  * fused deep+wide Adagrad: pass 1 (atomic accumulate, the existing
+    emb_bwd_sgd_fused_wide kernel on the accumulators), pass 2 (claim +
+    apply, sparse_adagrad.hip), and both together through the public op;
+  * the existing fused deep+wide SGD scatter (context, not a target:
+    pass 1 alone is the same atomic traffic);
+  * a torch baseline on the GPU: torch.unique (sort) + index_add_ +
+    row gather / elementwise / index_copy_ for both tables.
+
+Each figure is the median over --repeats windows of --iters calls (device
+events around each window, after a warm-up window), with min..max as the
+spread.  --zipf A draws ids from a Zipf(A) law instead of uniform.
+--json PATH also writes the numbers to a file."""
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tf_yarn_amd import ops  # noqa: E402
+
+F = 26
+DIM = 16
+LR, EPS = 0.01, 1e-10
+
+
+def timed(fn, iters, repeats):
+    """us per call: (median, min, max) over `repeats` event-timed windows."""
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        out.append(t0.elapsed_time(t1) * 1e3 / iters)
+    return statistics.median(out), min(out), max(out)
+
+
+def make_ids(batch, rows_per, zipf, seed):
+    rng = np.random.default_rng(seed)
+    if zipf > 0:
+        local = (rng.zipf(zipf, size=(batch, F)) - 1) % rows_per
+    else:
+        local = rng.integers(0, rows_per, size=(batch, F))
+    offs = (np.arange(F, dtype=np.int64) * rows_per)[None, :]
+    return torch.from_numpy((local + offs).reshape(-1)).cuda()
+
+
+def torch_baseline(table, state, wide, wide_state, ids, grad, gw):
+    uniq, inv = torch.unique(ids, return_inverse=True)
+    g = torch.zeros(uniq.numel(), DIM, device=ids.device)
+    g.index_add_(0, inv, grad.float())
+    s = state.index_select(0, uniq).addcmul_(g, g)
+    state.index_copy_(0, uniq, s)
+    table.index_copy_(0, uniq, table.index_select(0, uniq).addcdiv_(
+        g, s.sqrt_().add_(EPS), value=-LR))
+    g_div = ids.numel() // gw.numel()
+    gwide = torch.zeros(uniq.numel(), device=ids.device)
+    gwide.index_add_(0, inv, gw.float().repeat_interleave(g_div))
+    ws = wide_state.reshape(-1)
+    s1 = ws.index_select(0, uniq).addcmul_(gwide, gwide)
+    ws.index_copy_(0, uniq, s1)
+    wt = wide.reshape(-1)
+    wt.index_copy_(0, uniq, wt.index_select(0, uniq).addcdiv_(
+        gwide, s1.sqrt_().add_(EPS), value=-LR))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--rows-per-table", type=int, default=1_000_000)
+    ap.add_argument("--zipf", type=float, default=0.0,
+                    help="Zipf exponent (> 1) for the ids; 0 = uniform")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+
+    torch.manual_seed(0)
+    n_rows = args.rows_per_table * F
+    ids = make_ids(args.batch, args.rows_per_table, args.zipf, seed=0)
+    n = ids.numel()
+    grad = torch.randn(n, DIM, device="cuda").to(torch.bfloat16)
+    gw = torch.randn(args.batch, device="cuda").to(torch.bfloat16)
+    table = torch.randn(n_rows, DIM, device="cuda")
+    wide = torch.randn(n_rows, 1, device="cuda")
+    state = torch.zeros_like(table)
+    wide_state = torch.zeros_like(wide)
+    ws = ops.SparseAdagradWorkspace(table, wide)
+    uniq = int(torch.unique(ids).numel())
+    C = ops._C
+
+    res = {"batch": args.batch, "rows": n_rows, "updates": n,
+           "unique_rows": uniq, "zipf": args.zipf,
+           "iters": args.iters, "repeats": args.repeats}
+
+    def record(name, fn):
+        med, lo, hi = timed(fn, args.iters, args.repeats)
+        res[name] = {"median_us": round(med, 1), "min_us": round(lo, 1),
+                     "max_us": round(hi, 1)}
+        print(f"{name:28s} {med:8.1f} us  ({lo:.1f} .. {hi:.1f})",
+              flush=True)
+
+    record("sgd_fused_wide", lambda: C.emb_bwd_sgd_fused_wide(
+        table, wide, ids, grad, gw, LR, 1.0))
+    record("adagrad_pass1_accumulate", lambda: C.emb_bwd_sgd_fused_wide(
+        ws.acc, ws.wide_acc, ids, grad, gw, -1.0, 1.0))
+    # consumes the accumulated sums once, then runs on a clean
+    # accumulator: same claims and row traffic every call
+    record("adagrad_pass2_claim_apply",
+           lambda: C.sparse_adagrad_apply_fused_wide(
+               table, state, ws.acc, wide, wide_state, ws.wide_acc,
+               ws.stamp, ids, ws.next_epoch(), LR, EPS))
+    assert not ws.acc.any() and not ws.wide_acc.any()
+    record("adagrad_fused_wide_total",
+           lambda: ops.emb_bwd_adagrad_fused_wide(
+               table, state, wide, wide_state, ids, grad, gw, lr=LR,
+               eps=EPS, workspace=ws))
+    record("adagrad_deep_only", lambda: ops.emb_bwd_adagrad(
+        table, state, ids, grad, lr=LR, eps=EPS, workspace=ws))
+    record("adagrad_wide_only", lambda: ops.emb_bwd_adagrad_wide(
+        wide, wide_state, ids, gw, lr=LR, eps=EPS,
+        workspace=ws.wide_view()))
+    record("torch_unique_index_add", lambda: torch_baseline(
+        table, state, wide, wide_state, ids, grad, gw))
+
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)),
+                    exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

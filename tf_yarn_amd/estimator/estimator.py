@@ -231,7 +231,9 @@ class Estimator:
                         self.grad_sync_hook(module)
                     optimizer.step()
                     if hasattr(module, "apply_sparse_updates"):
-                        # sink-based embedding grads (CTR models)
+                        # sink-based embedding grads (CTR models); the
+                        # update rule is the model's sparse_optimizer,
+                        # only the lr is taken from the dense optimizer
                         module.apply_sparse_updates(
                             optimizer.param_groups[0].get("lr", 0.0))
                 self.global_step += 1

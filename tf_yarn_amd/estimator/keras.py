@@ -158,7 +158,9 @@ class KerasModel:
         """CTR models (WideAndDeep) route embedding grads through a
         sink instead of p.grad; apply the fused sparse update with the
         optimizer's lr (and clear the sink so eval passes don't leak).
-        No-op for ordinary modules."""
+        Only the lr comes from the optimizer: SGD vs Adagrad on the
+        tables is the model's ``sparse_optimizer`` argument, never
+        inferred from the dense optimizer.  No-op for ordinary modules."""
         m = self.module
         if hasattr(m, "apply_sparse_updates"):
             lr = self.optimizer.param_groups[0].get("lr", 0.0)

@@ -36,6 +36,7 @@ import torch.distributed as dist
 from torch import nn
 
 from tf_yarn_amd import ops
+from tf_yarn_amd.models.wide_deep import SparseOptimizerMixin
 from tf_yarn_amd.utils import commprobe
 
 logger = logging.getLogger(__name__)
@@ -287,17 +288,24 @@ class _ShardedLookup(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
-class ShardedCriteoEmbeddings(nn.Module):
+class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
     """Deep (dim-D) + wide (dim-1) categorical embeddings, feature-sharded
     across the process group.  ``forward(ids, deep_out_buf, col_offset)``
     fills ``deep_out_buf[:, col_offset:]`` with [B, F*D] (owner-permuted
     feature order, consistent across steps) and returns the wide sums [B].
+
+    ``sparse_optimizer="adagrad"`` makes the owner-local update sparse
+    Adagrad (``state_sum`` / ``wide_state_sum`` buffers, per rank like the
+    tables).  The binned scatter and its forward-time permutation
+    prefetch are SGD-only and are skipped under Adagrad.
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
                  out_bf16: bool = False, process_group=None,
                  init_std: Optional[float] = None,
-                 wide_init_std: float = 0.01):
+                 wide_init_std: float = 0.01,
+                 sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
+                 sparse_initial_accumulator: float = 0.0):
         super().__init__()
         import math
         self.F = len(table_sizes)
@@ -320,6 +328,9 @@ class ShardedCriteoEmbeddings(nn.Module):
             torch.randn(total_own, 1) * wide_init_std)
         self.wide_weight._miyarn_sparse = True
         self.wide_weight._miyarn_sharded = True
+        self._init_sparse_optimizer(
+            sparse_optimizer, sparse_eps, sparse_initial_accumulator,
+            {"state_sum": self.weight, "wide_state_sum": self.wide_weight})
         offs = torch.tensor(
             [0] + list(torch.cumsum(torch.tensor(own_sizes), 0)[:-1]),
             dtype=torch.int64)
@@ -370,7 +381,8 @@ class ShardedCriteoEmbeddings(nn.Module):
 
     @torch.no_grad()
     def apply_sparse_updates(self, lr: float, stream=None) -> None:
-        """Owner-local fused scatter+SGD; scale 1/world (grads come from a
+        """Owner-local fused scatter+SGD (or sparse Adagrad, see
+        ``sparse_optimizer``); scale 1/world (grads come from a
         global-mean loss split across ranks).
 
         ``stream``: optional side HIP stream.  The scatters are atomic-
@@ -396,6 +408,8 @@ class ShardedCriteoEmbeddings(nn.Module):
         stream DURING FORWARD: it depends only on the ids, and its
         ~200 us of latency/atomic-bound work hides under the MFMA-bound
         MLP GEMMs instead of sitting on the backward critical path."""
+        if self.sparse_optimizer != "sgd":
+            return  # the binned scatter is an SGD kernel
         if not (flat_ids.is_cuda and self.dim == 16 and ops.HAVE_EXT
                 and torch.is_grad_enabled() and self._binned_on(flat_ids)):
             return
@@ -437,7 +451,45 @@ class ShardedCriteoEmbeddings(nn.Module):
                 "binned-dedup" if self._binned_auto else "atomic")
         return self._binned_auto
 
+    def _apply_pending_adagrad(self, lr: float) -> None:
+        """Sparse Adagrad on the owner-local tables.  Deep and wide sink
+        entries that share their flat ids take the fused deep+wide entry
+        (ids read once per pass, one claim per row for both tables), as
+        the SGD path does; the binned scatter is never used here."""
+        scale = 1.0 / self.world
+        ws = self._adagrad_workspace(self.weight.data,
+                                     self.wide_weight.data)
+        wide_by_ids = {gw_ids.data_ptr(): (i, gw)
+                       for i, (gw_ids, gw) in enumerate(self._wide_sink)}
+        fused_wide_done = set()
+        for flat_ids, grad in self._deep_sink:
+            grad2d = grad.reshape(flat_ids.numel(), self.dim)
+            mate = wide_by_ids.get(flat_ids.data_ptr())
+            if mate is not None and mate[0] not in fused_wide_done:
+                ops.emb_bwd_adagrad_fused_wide(
+                    self.weight.data, self.state_sum,
+                    self.wide_weight.data, self.wide_state_sum, flat_ids,
+                    grad2d, mate[1], lr=lr, eps=self.sparse_eps,
+                    scale=scale, workspace=ws)
+                fused_wide_done.add(mate[0])
+            else:
+                ops.emb_bwd_adagrad(
+                    self.weight.data, self.state_sum, flat_ids, grad2d,
+                    lr=lr, eps=self.sparse_eps, scale=scale, workspace=ws)
+        self._deep_sink.clear()
+        for i, (flat_ids, gw) in enumerate(self._wide_sink):
+            if i in fused_wide_done:
+                continue
+            ops.emb_bwd_adagrad_wide(
+                self.wide_weight.data, self.wide_state_sum, flat_ids, gw,
+                lr=lr, eps=self.sparse_eps, scale=scale,
+                workspace=ws.wide_view())
+        self._wide_sink.clear()
+
     def _apply_pending(self, lr: float) -> None:
+        if self.sparse_optimizer == "adagrad":
+            self._apply_pending_adagrad(lr)
+            return
         scale = 1.0 / self.world
         # Binned scatter (round-2 kernel): one region-binned permutation
         # shared by the deep and wide updates (identical flat ids), LDS

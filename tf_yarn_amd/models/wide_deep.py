@@ -40,6 +40,104 @@ CRITEO_SPARSE = 26
 DEFAULT_TABLE_SIZES = [1_000_000] * CRITEO_SPARSE
 
 
+SPARSE_OPTIMIZERS = ("sgd", "adagrad")
+
+
+class SparseOptimizerMixin:
+    """Per-table sparse-optimizer choice for the embedding modules.
+
+    The sparse optimizer is chosen ON THE MODEL (``sparse_optimizer=``),
+    never inferred from the dense optimizer; ``apply_sparse_updates(lr)``
+    keeps its signature and branches on the mode.  ``"sgd"`` (default)
+    adds no attribute that shows in ``state_dict``, no memory and no
+    kernel.  ``"adagrad"`` adds, per table:
+
+    * ``<state name>``: persistent fp32 buffer shaped like the table,
+      filled with ``sparse_initial_accumulator`` (checkpoints carry it);
+    * a non-persistent accumulator + int32 row stamp, allocated on the
+      first apply (:class:`tf_yarn_amd.ops.SparseAdagradWorkspace`).
+
+    All of them are flagged ``_miyarn_sharded`` in every mode so
+    ``BucketedDataParallel`` never re-broadcasts a table-sized buffer per
+    forward; replicated tables stay consistent because every rank applies
+    the same allgathered updates."""
+
+    def _init_sparse_optimizer(self, sparse_optimizer: str,
+                               sparse_eps: float,
+                               sparse_initial_accumulator: float,
+                               states: dict) -> None:
+        """``states``: state buffer name -> the table parameter it
+        follows; the first entry owns the row stamp."""
+        if sparse_optimizer not in SPARSE_OPTIMIZERS:
+            raise ValueError(
+                f"sparse_optimizer must be one of {SPARSE_OPTIMIZERS}, "
+                f"got {sparse_optimizer!r}")
+        self.sparse_optimizer = sparse_optimizer
+        self.sparse_eps = float(sparse_eps)
+        self._sparse_buffer_names: List[str] = []
+        self._sparse_ws: Optional[ops.SparseAdagradWorkspace] = None
+        if sparse_optimizer != "adagrad":
+            return
+        for i, (name, table) in enumerate(states.items()):
+            self.register_buffer(
+                name, torch.full_like(table.detach(),
+                                      float(sparse_initial_accumulator)),
+                persistent=True)
+            acc = "_adagrad_acc" if i == 0 else f"_adagrad_acc{i}"
+            self.register_buffer(acc, None, persistent=False)
+            self._sparse_buffer_names += [name, acc]
+        self.register_buffer("_adagrad_stamp", None, persistent=False)
+        self._sparse_buffer_names.append("_adagrad_stamp")
+        self._flag_sparse_buffers()
+
+    def _flag_sparse_buffers(self) -> None:
+        for name in getattr(self, "_sparse_buffer_names", ()):
+            buf = getattr(self, name)
+            if buf is not None:
+                buf._miyarn_sharded = True
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to()/.cuda() replace buffer tensors: carry the flag over
+        super()._apply(fn, *args, **kwargs)
+        self._flag_sparse_buffers()
+        return self
+
+    def __getstate__(self):
+        # whole-module pickles (Keras ``save``) and deepcopies leave the
+        # scratch behind: it is all-zero / restartable between applies
+        state = self.__dict__.copy()
+        if state.get("_sparse_ws") is not None:
+            state["_sparse_ws"] = None
+            buffers = state["_buffers"] = state["_buffers"].copy()
+            for name in self._sparse_buffer_names:
+                if name.startswith("_adagrad"):
+                    buffers[name] = None
+        return state
+
+    def _adagrad_workspace(self, table: torch.Tensor,
+                           wide_table: Optional[torch.Tensor] = None
+                           ) -> "ops.SparseAdagradWorkspace":
+        """The module's workspace, bound to its non-persistent buffers
+        (allocated on first use, re-bound after a device move)."""
+        ws = self._sparse_ws
+        if ws is None:
+            ws = ops.SparseAdagradWorkspace(table, wide_table)
+            self._sparse_ws = ws
+            self._adagrad_acc = ws.acc
+            if wide_table is not None:
+                self._adagrad_acc1 = ws.wide_acc
+            self._adagrad_stamp = ws.stamp
+            self._flag_sparse_buffers()
+        elif ws.stamp is not self._adagrad_stamp:
+            # .to()/unpickling replaced the buffer tensors but kept their
+            # contents (zero acc, stamps of past epochs): re-bind
+            ws.acc = self._adagrad_acc
+            if wide_table is not None:
+                ws.wide_acc = self._adagrad_acc1
+            ws.stamp = self._adagrad_stamp
+        return ws
+
+
 class _FusedLookup(torch.autograd.Function):
     """Gather via the HIP kernel; backward stashes sparse (ids, grad)."""
 
@@ -57,16 +155,20 @@ class _FusedLookup(torch.autograd.Function):
         return None, None, None, None
 
 
-class SparseEmbedding(nn.Module):
+class SparseEmbedding(SparseOptimizerMixin, nn.Module):
     """Fused multi-table embedding with sparse-allgather DP sync.
 
     ``forward(ids [B, F])`` -> ``[B, F*dim]``.
     After ``loss.backward()`` call :meth:`apply_sparse_updates` (the
     training loop or the framework optimizer wrapper does this).
+    ``sparse_optimizer="adagrad"`` replaces the scatter+SGD update with
+    sparse Adagrad (state in the ``state_sum`` buffer).
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
-                 out_bf16: bool = False, init_std: Optional[float] = None):
+                 out_bf16: bool = False, init_std: Optional[float] = None,
+                 sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
+                 sparse_initial_accumulator: float = 0.0):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.dim = dim
@@ -80,6 +182,9 @@ class SparseEmbedding(nn.Module):
         weight = torch.randn(total, dim) * std
         self.weight = nn.Parameter(weight)
         self.weight._miyarn_sparse = True  # dense reducer must skip it
+        self._init_sparse_optimizer(sparse_optimizer, sparse_eps,
+                                    sparse_initial_accumulator,
+                                    {"state_sum": self.weight})
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -125,12 +230,18 @@ class SparseEmbedding(nn.Module):
 
     @torch.no_grad()
     def finish_sparse_sync(self, lr: float) -> None:
-        """Wait for the allgathers and apply the fused scatter+SGD update
-        scaled by 1/world_size."""
+        """Wait for the allgathers and apply the fused scatter+SGD (or
+        sparse Adagrad) update scaled by 1/world_size."""
         world = getattr(self, "_pending_world", 1)
         for all_ids, all_grads, works in getattr(self, "_gathered", []):
             for w in works:
                 w.wait()
+            if self.sparse_optimizer == "adagrad":
+                ops.emb_bwd_adagrad(
+                    self.weight.data, self.state_sum, all_ids, all_grads,
+                    lr=lr, eps=self.sparse_eps, scale=1.0 / world,
+                    workspace=self._adagrad_workspace(self.weight.data))
+                continue
             ops.emb_bwd_sgd(self.weight.data, all_ids, all_grads,
                             lr=lr, scale=1.0 / world)
         self._gathered = []
@@ -168,12 +279,16 @@ class _GatherSum(torch.autograd.Function):
         return None, None, None, None, None
 
 
-class WideScalarEmbedding(nn.Module):
+class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
     """Per-id scalar weights with fused gather-sum forward and
-    scatter-add sparse update (the wide part of wide-and-deep)."""
+    scatter-add sparse update (the wide part of wide-and-deep);
+    ``sparse_optimizer="adagrad"`` switches the update to sparse
+    Adagrad."""
 
     def __init__(self, table_sizes: List[int], out_bf16: bool = False,
-                 init_std: float = 0.01):
+                 init_std: float = 0.01, sparse_optimizer: str = "sgd",
+                 sparse_eps: float = 1e-10,
+                 sparse_initial_accumulator: float = 0.0):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.out_bf16 = out_bf16
@@ -184,6 +299,9 @@ class WideScalarEmbedding(nn.Module):
         self.register_buffer("offsets", offsets, persistent=True)
         self.weight = nn.Parameter(torch.randn(total, 1) * init_std)
         self.weight._miyarn_sparse = True
+        self._init_sparse_optimizer(sparse_optimizer, sparse_eps,
+                                    sparse_initial_accumulator,
+                                    {"state_sum": self.weight})
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -229,6 +347,12 @@ class WideScalarEmbedding(nn.Module):
         for all_ids, all_grads, works in getattr(self, "_gathered", []):
             for w in works:
                 w.wait()
+            if self.sparse_optimizer == "adagrad":
+                ops.emb_bwd_adagrad_wide(
+                    self.weight.data, self.state_sum, all_ids, all_grads,
+                    lr=lr, eps=self.sparse_eps, scale=1.0 / world,
+                    workspace=self._adagrad_workspace(self.weight.data))
+                continue
             ops.emb_scatter_sum(self.weight.data,
                                 all_ids.reshape(all_grads.numel(), -1),
                                 all_grads, alpha=-lr / world)
@@ -333,9 +457,20 @@ class WideAndDeep(nn.Module):
                  hidden: Tuple[int, ...] = (1024, 512, 256),
                  compute_dtype: torch.dtype = torch.float32,
                  sharded: bool = False,
-                 process_group=None):
+                 process_group=None,
+                 sparse_optimizer: str = "sgd",
+                 sparse_eps: float = 1e-10,
+                 sparse_initial_accumulator: float = 0.0):
+        """``sparse_optimizer`` ("sgd" or "adagrad") picks the update rule
+        of the embedding tables; it is NOT inferred from the dense
+        optimizer, whose lr is what ``apply_sparse_updates(lr)``
+        receives."""
         super().__init__()
         table_sizes = table_sizes or DEFAULT_TABLE_SIZES
+        sparse_kw = dict(
+            sparse_optimizer=sparse_optimizer, sparse_eps=sparse_eps,
+            sparse_initial_accumulator=sparse_initial_accumulator)
+        self.sparse_optimizer = sparse_optimizer
         self.compute_dtype = compute_dtype
         self.dense_dim = dense_dim
         bf16 = compute_dtype == torch.bfloat16
@@ -345,16 +480,17 @@ class WideAndDeep(nn.Module):
                 ShardedCriteoEmbeddings
             self.embeddings = ShardedCriteoEmbeddings(
                 table_sizes, embedding_dim, out_bf16=bf16,
-                process_group=process_group)
+                process_group=process_group, **sparse_kw)
             self.deep_embedding = None
             self.wide_embedding = None
         else:
             self.embeddings = None
             self.deep_embedding = SparseEmbedding(
-                table_sizes, embedding_dim, out_bf16=bf16)
+                table_sizes, embedding_dim, out_bf16=bf16, **sparse_kw)
             # Wide: one scalar weight per categorical id
             self.wide_embedding = WideScalarEmbedding(table_sizes,
-                                                      out_bf16=bf16)
+                                                      out_bf16=bf16,
+                                                      **sparse_kw)
         self.wide_dense = ScalarHead(dense_dim, compute_dtype)
         layers: List[nn.Module] = []
         # dense block padded to 16 columns for quad-aligned fused gather
@@ -442,10 +578,16 @@ class FlatInputWideAndDeep(nn.Module):
                  embedding_dim: int = 16,
                  hidden: Tuple[int, ...] = (1024, 512, 256),
                  compute_dtype: torch.dtype = torch.float32,
-                 sharded: bool = False, process_group=None):
+                 sharded: bool = False, process_group=None,
+                 sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
+                 sparse_initial_accumulator: float = 0.0):
         super().__init__()
         self.dense_dim = dense_dim
+        init_acc = sparse_initial_accumulator
         self.net = WideAndDeep(dense_dim=dense_dim,
+                               sparse_optimizer=sparse_optimizer,
+                               sparse_eps=sparse_eps,
+                               sparse_initial_accumulator=init_acc,
                                table_sizes=table_sizes,
                                embedding_dim=embedding_dim, hidden=hidden,
                                compute_dtype=compute_dtype,

@@ -286,6 +286,173 @@ def emb_bwd_dense(grad_table: torch.Tensor, ids: torch.Tensor,
                           alpha=scale)
 
 
+# ---- sparse Adagrad --------------------------------------------------------
+
+class SparseAdagradWorkspace:
+    """Device scratch of the accumulate-then-claim sparse Adagrad kernels
+    for one table (optionally with its ``[rows, 1]`` wide companion).
+
+    ``acc`` (and ``wide_acc``): fp32, shaped like the table, ALL-ZERO
+    between calls — pass 1 scatter-adds into it and pass 2 zeroes every
+    row it consumes.  ``stamp``: int32 per row, zero-initialised; a row is
+    claimed by exchanging the current ``epoch`` into it.  ``epoch`` starts
+    at 1 and advances on every apply launch, so the stamp is never
+    cleared (except once per 2^31 launches, when the counter wraps).
+    Cost: one extra table-sized fp32 buffer + 4 B/row."""
+
+    _EPOCH_MAX = 2 ** 31 - 2
+
+    def __init__(self, table: torch.Tensor,
+                 wide_table: Optional[torch.Tensor] = None):
+        self.acc = torch.zeros_like(table)
+        self.wide_acc = (torch.zeros_like(wide_table)
+                         if wide_table is not None else None)
+        self.stamp = torch.zeros(table.shape[0], dtype=torch.int32,
+                                 device=table.device)
+        self.epoch = 0  # last epoch handed out
+
+    def next_epoch(self) -> int:
+        if self.epoch >= self._EPOCH_MAX:
+            self.stamp.zero_()
+            self.epoch = 0
+        self.epoch += 1
+        return self.epoch
+
+    def wide_view(self) -> "_WideWorkspaceView":
+        """The wide table's single-table face of a deep+wide workspace:
+        ``wide_acc`` with the shared stamp and epoch counter."""
+        return _WideWorkspaceView(self)
+
+
+class _WideWorkspaceView:
+    def __init__(self, ws: SparseAdagradWorkspace):
+        self._ws = ws
+
+    @property
+    def acc(self) -> torch.Tensor:
+        return self._ws.wide_acc
+
+    @property
+    def stamp(self) -> torch.Tensor:
+        return self._ws.stamp
+
+    def next_epoch(self) -> int:
+        return self._ws.next_epoch()
+
+
+def _adagrad_rows_ref(table: torch.Tensor, state_sum: torch.Tensor,
+                      flat_ids: torch.Tensor, rows: torch.Tensor,
+                      lr: float, eps: float, scale: float) -> None:
+    """Reference: coalesce duplicate ids, then one Adagrad step on the
+    unique rows (== torch.optim.Adagrad on a coalesced sparse grad)."""
+    uniq, inv = torch.unique(flat_ids, return_inverse=True)
+    g = torch.zeros(uniq.numel(), rows.shape[1], dtype=torch.float32,
+                    device=rows.device)
+    g.index_add_(0, inv, rows.float())
+    g.mul_(scale)
+    s = state_sum.index_select(0, uniq).addcmul_(g, g, value=1.0)
+    state_sum.index_copy_(0, uniq, s)
+    w = table.index_select(0, uniq).addcdiv_(g, s.sqrt().add_(eps),
+                                             value=-lr)
+    table.index_copy_(0, uniq, w)
+
+
+def emb_bwd_adagrad(table: torch.Tensor, state_sum: torch.Tensor,
+                    ids: torch.Tensor, grad: torch.Tensor, *, lr: float,
+                    eps: float = 1e-10, scale: float = 1.0,
+                    workspace: Optional[SparseAdagradWorkspace] = None
+                    ) -> None:
+    """Sparse Adagrad on the rows named by ``ids``.  For each unique id u:
+    ``G = scale * sum(grad[i] for ids[i] == u)``; ``state_sum[u] += G*G``;
+    ``table[u] -= lr * G / (sqrt(state_sum[u]) + eps)``.  Rows not in
+    ``ids`` are neither read nor written.  ``grad`` fp32 or bf16, table
+    and state fp32, any ``dim >= 1``.
+
+    GPU: atomic scatter into ``workspace.acc`` (the existing
+    ``emb_bwd_dense`` kernel), then the claim kernel updates each touched
+    row exactly once (``csrc/sparse_adagrad.hip``).  Pass a persistent
+    :class:`SparseAdagradWorkspace`; without one a table-sized scratch is
+    allocated for the call."""
+    flat = ids.reshape(-1)
+    if _on_gpu(table, state_sum, ids, grad):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseAdagradWorkspace(table)
+        _C.emb_bwd_adagrad(table, state_sum, ws.acc, ws.stamp,
+                           flat.contiguous(), grad.contiguous(),
+                           ws.next_epoch(), lr, eps, scale)
+        return
+    _adagrad_rows_ref(table, state_sum, flat,
+                      grad.reshape(flat.numel(), -1), lr, eps, scale)
+
+
+def emb_bwd_adagrad_wide(table: torch.Tensor, state_sum: torch.Tensor,
+                         ids: torch.Tensor, gw: torch.Tensor, *, lr: float,
+                         eps: float = 1e-10, scale: float = 1.0,
+                         workspace: Optional[SparseAdagradWorkspace] = None
+                         ) -> None:
+    """:func:`emb_bwd_adagrad` for the ``[rows, 1]`` wide table: the
+    gradient of flat update i is the per-example ``gw[i // g_div]``,
+    ``g_div = ids.numel() // gw.numel()`` (layout of
+    :func:`emb_scatter_sum`)."""
+    flat = ids.reshape(-1)
+    if _on_gpu(table, state_sum, ids, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseAdagradWorkspace(table)
+        _C.emb_bwd_adagrad_wide(table, state_sum, ws.acc, ws.stamp,
+                                flat.contiguous(),
+                                gw.reshape(-1).contiguous(),
+                                ws.next_epoch(), lr, eps, scale)
+        return
+    if flat.numel() == 0:
+        return
+    g_div = flat.numel() // gw.numel()
+    rows = gw.float().reshape(-1, 1).expand(-1, g_div).reshape(-1, 1)
+    _adagrad_rows_ref(table.reshape(-1, 1), state_sum.reshape(-1, 1), flat,
+                      rows, lr, eps, scale)
+
+
+def emb_bwd_adagrad_fused_wide(table: torch.Tensor, state_sum: torch.Tensor,
+                               wide_table: torch.Tensor,
+                               wide_state_sum: torch.Tensor,
+                               ids: torch.Tensor, grad: torch.Tensor,
+                               gw: torch.Tensor, *, lr: float,
+                               eps: float = 1e-10, scale: float = 1.0,
+                               workspace: Optional[
+                                   SparseAdagradWorkspace] = None) -> None:
+    """Sparse Adagrad on BOTH CTR tables from the shared flat ids (the
+    Adagrad mirror of :func:`emb_bwd_sgd_fused_wide`): the ids are read
+    once per pass and the winner of a deep row also applies the wide
+    scalar.  ``workspace`` must have been built with ``wide_table``.
+    Shapes the fused kernels do not cover (``dim/4`` not a power of two
+    <= 64, mixed grad dtypes) take the two single-table ops, sharing the
+    workspace's stamp across two epochs."""
+    if _on_gpu(table, ids, grad, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseAdagradWorkspace(table, wide_table)
+        dvec, rem = divmod(table.shape[1], 4)
+        if (rem == 0 and 1 <= dvec <= 64 and dvec & (dvec - 1) == 0
+                and grad.dtype == gw.dtype):
+            _C.emb_bwd_adagrad_fused_wide(
+                table, state_sum, ws.acc, wide_table, wide_state_sum,
+                ws.wide_acc, ws.stamp, ids.reshape(-1).contiguous(),
+                grad.contiguous(), gw.reshape(-1).contiguous(),
+                ws.next_epoch(), lr, eps, scale)
+            return
+        emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
+                        scale=scale, workspace=ws)
+        emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
+                             eps=eps, scale=scale,
+                             workspace=ws.wide_view())
+        return
+    emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
+                    scale=scale)
+    emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
+                         eps=eps, scale=scale)
+
+
 # ---- elementwise -----------------------------------------------------------
 
 def bias_relu_fwd(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:

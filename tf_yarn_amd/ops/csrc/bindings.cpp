@@ -49,6 +49,32 @@ void emb_fwd_into(torch::Tensor table, torch::Tensor ids,
 void emb_scatter_sum(torch::Tensor table, torch::Tensor ids,
                      torch::Tensor grad, double alpha);
 
+// sparse_adagrad.hip
+void sparse_adagrad_apply(torch::Tensor table, torch::Tensor state_sum,
+                          torch::Tensor acc, torch::Tensor stamp,
+                          torch::Tensor ids, int64_t epoch, double lr,
+                          double eps);
+void sparse_adagrad_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    int64_t epoch, double lr, double eps);
+void emb_bwd_adagrad(torch::Tensor table, torch::Tensor state_sum,
+                     torch::Tensor acc, torch::Tensor stamp,
+                     torch::Tensor ids, torch::Tensor grad, int64_t epoch,
+                     double lr, double eps, double scale);
+void emb_bwd_adagrad_wide(torch::Tensor table, torch::Tensor state_sum,
+                          torch::Tensor acc, torch::Tensor stamp,
+                          torch::Tensor ids, torch::Tensor gw,
+                          int64_t epoch, double lr, double eps,
+                          double scale);
+void emb_bwd_adagrad_fused_wide(
+    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
+    double eps, double scale);
+
 // binned_scatter.hip
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
                                               int64_t n_rows,
@@ -112,6 +138,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused deep scatter+SGD + wide scalar scatter (shared ids)");
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
+  m.def("sparse_adagrad_apply", &sparse_adagrad_apply,
+        "Sparse Adagrad pass 2: claim each touched row once, consume the "
+        "accumulator, update state + table");
+  m.def("sparse_adagrad_apply_fused_wide", &sparse_adagrad_apply_fused_wide,
+        "Sparse Adagrad pass 2 for the deep + wide pair (shared ids)");
+  m.def("emb_bwd_adagrad", &emb_bwd_adagrad,
+        "Sparse Adagrad: atomic accumulate + once-per-row claim/apply");
+  m.def("emb_bwd_adagrad_wide", &emb_bwd_adagrad_wide,
+        "Sparse Adagrad for the [rows, 1] wide table (gw[i / g_div])");
+  m.def("emb_bwd_adagrad_fused_wide", &emb_bwd_adagrad_fused_wide,
+        "Sparse Adagrad for the deep + wide pair (shared ids)");
   m.def("bias_relu_fwd", &bias_relu_fwd, "Fused bias+ReLU forward");
   m.def("bias_relu_bwd", &bias_relu_bwd, "Fused ReLU backward");
   m.def("lt_linear", &lt_linear,
