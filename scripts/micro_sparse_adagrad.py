@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the sparse Adagrad apply at the bench shape
-(b=65536, 26 features x 1M rows, dim 16 deep + dim 1 wide, bf16 grads).
+"""Micro-benchmark of the stateful sparse apply (Adagrad, FTRL) at the
+bench shape (b=65536, 26 features x 1M rows, dim 16 deep + dim 1 wide,
+bf16 grads).  --rule picks the update rule: adagrad (both tables), ftrl
+(both tables) or adagrad+ftrl (deep Adagrad, wide FTRL: the
+wide-and-deep recipe).
 
 Timed, on identical inputs:
-  * fused deep+wide Adagrad: pass 1 (atomic accumulate, the existing
+  * the fused deep+wide update: pass 1 (atomic accumulate, the existing
     emb_bwd_sgd_fused_wide kernel on the accumulators), pass 2 (claim +
     apply, sparse_adagrad.hip), and both together through the public op;
   * the existing fused deep+wide SGD scatter (context, not a target:
     pass 1 alone is the same atomic traffic);
   * a torch baseline on the GPU: torch.unique (sort) + index_add_ +
-    row gather / elementwise / index_copy_ for both tables.
+    row gather / the same rule elementwise / index_copy_ for both tables.
 
 Each figure is the median over --repeats windows of --iters calls (device
 events around each window, after a warm-up window), with min..max as the
@@ -31,6 +34,7 @@ from tf_yarn_amd import ops  # noqa: E402
 F = 26
 DIM = 16
 LR, EPS = 0.01, 1e-10
+L1, L2 = 0.001, 0.001  # FTRL
 
 
 def timed(fn, iters, repeats):
@@ -61,23 +65,39 @@ def make_ids(batch, rows_per, zipf, seed):
     return torch.from_numpy((local + offs).reshape(-1)).cuda()
 
 
-def torch_baseline(table, state, wide, wide_state, ids, grad, gw):
+def _baseline_rows(rule, table, states, uniq, g):
+    """One table of the torch baseline: gather the unique rows, apply the
+    rule elementwise, copy back.  The FTRL rule is the one `ops` uses."""
+    w = table.index_select(0, uniq)
+    if rule == "adagrad":
+        s = states[0].index_select(0, uniq).addcmul_(g, g)
+        states[0].index_copy_(0, uniq, s)
+        table.index_copy_(0, uniq, w.addcdiv_(g, s.sqrt_().add_(EPS),
+                                              value=-LR))
+        return
+    n, z, w = ops._ftrl_rule(g, states[0].index_select(0, uniq),
+                             states[1].index_select(0, uniq), w, LR, L1, L2)
+    states[0].index_copy_(0, uniq, n)
+    states[1].index_copy_(0, uniq, z)
+    table.index_copy_(0, uniq, w)
+
+
+def torch_baseline(rules, table, states, wide, wide_states, ids, grad, gw):
     uniq, inv = torch.unique(ids, return_inverse=True)
     g = torch.zeros(uniq.numel(), DIM, device=ids.device)
     g.index_add_(0, inv, grad.float())
-    s = state.index_select(0, uniq).addcmul_(g, g)
-    state.index_copy_(0, uniq, s)
-    table.index_copy_(0, uniq, table.index_select(0, uniq).addcdiv_(
-        g, s.sqrt_().add_(EPS), value=-LR))
+    _baseline_rows(rules[0], table, states, uniq, g)
     g_div = ids.numel() // gw.numel()
     gwide = torch.zeros(uniq.numel(), device=ids.device)
     gwide.index_add_(0, inv, gw.float().repeat_interleave(g_div))
-    ws = wide_state.reshape(-1)
-    s1 = ws.index_select(0, uniq).addcmul_(gwide, gwide)
-    ws.index_copy_(0, uniq, s1)
-    wt = wide.reshape(-1)
-    wt.index_copy_(0, uniq, wt.index_select(0, uniq).addcdiv_(
-        gwide, s1.sqrt_().add_(EPS), value=-LR))
+    _baseline_rows(rules[1], wide.reshape(-1),
+                   [s.reshape(-1) for s in wide_states], uniq, gwide)
+
+
+def make_states(rule, table):
+    if rule == "adagrad":
+        return [torch.zeros_like(table)]
+    return [torch.full_like(table, 0.1), torch.zeros_like(table)]
 
 
 def main():
@@ -86,11 +106,16 @@ def main():
     ap.add_argument("--rows-per-table", type=int, default=1_000_000)
     ap.add_argument("--zipf", type=float, default=0.0,
                     help="Zipf exponent (> 1) for the ids; 0 = uniform")
+    ap.add_argument("--rule", default="adagrad",
+                    choices=["adagrad", "ftrl", "adagrad+ftrl"],
+                    help="update rule of the deep[+wide] table")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
+    rules = tuple(args.rule.split("+")) * (1 if "+" in args.rule else 2)
+    tag = args.rule.replace("+", "_")
 
     torch.manual_seed(0)
     n_rows = args.rows_per_table * F
@@ -100,45 +125,79 @@ def main():
     gw = torch.randn(args.batch, device="cuda").to(torch.bfloat16)
     table = torch.randn(n_rows, DIM, device="cuda")
     wide = torch.randn(n_rows, 1, device="cuda")
-    state = torch.zeros_like(table)
-    wide_state = torch.zeros_like(wide)
-    ws = ops.SparseAdagradWorkspace(table, wide)
+    states = make_states(rules[0], table)
+    wide_states = make_states(rules[1], wide)
+    ws = ops.SparseWorkspace(table, wide)
     uniq = int(torch.unique(ids).numel())
     C = ops._C
 
-    res = {"batch": args.batch, "rows": n_rows, "updates": n,
-           "unique_rows": uniq, "zipf": args.zipf,
+    res = {"rule": args.rule, "batch": args.batch, "rows": n_rows,
+           "updates": n, "unique_rows": uniq, "zipf": args.zipf,
            "iters": args.iters, "repeats": args.repeats}
 
     def record(name, fn):
         med, lo, hi = timed(fn, args.iters, args.repeats)
         res[name] = {"median_us": round(med, 1), "min_us": round(lo, 1),
                      "max_us": round(hi, 1)}
-        print(f"{name:28s} {med:8.1f} us  ({lo:.1f} .. {hi:.1f})",
+        print(f"{name:32s} {med:8.1f} us  ({lo:.1f} .. {hi:.1f})",
               flush=True)
+
+    if args.rule == "adagrad":
+        def pass2():
+            C.sparse_adagrad_apply_fused_wide(
+                table, states[0], ws.acc, wide, wide_states[0],
+                ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
+
+        def total():
+            ops.emb_bwd_adagrad_fused_wide(
+                table, states[0], wide, wide_states[0], ids, grad, gw,
+                lr=LR, eps=EPS, workspace=ws)
+    elif args.rule == "ftrl":
+        def pass2():
+            C.sparse_ftrl_apply_fused_wide(
+                table, *states, ws.acc, wide, *wide_states, ws.wide_acc,
+                ws.stamp, ids, ws.next_epoch(), LR, LR, L1, L2)
+
+        def total():
+            ops.emb_bwd_ftrl_fused_wide(
+                table, *states, wide, *wide_states, ids, grad, gw, lr=LR,
+                l1=L1, l2=L2, workspace=ws)
+    else:
+        def pass2():
+            C.sparse_adagrad_ftrl_apply_fused_wide(
+                table, states[0], ws.acc, wide, *wide_states, ws.wide_acc,
+                ws.stamp, ids, ws.next_epoch(), LR, EPS, LR, L1, L2)
+
+        def total():
+            ops.emb_bwd_adagrad_ftrl_fused_wide(
+                table, states[0], wide, *wide_states, ids, grad, gw,
+                lr=LR, eps=EPS, l1=L1, l2=L2, workspace=ws)
+
+    def single(rule, tbl, sts, g, workspace, wide_table):
+        if rule == "adagrad":
+            fn = ops.emb_bwd_adagrad_wide if wide_table \
+                else ops.emb_bwd_adagrad
+            return lambda: fn(tbl, sts[0], ids, g, lr=LR, eps=EPS,
+                              workspace=workspace)
+        fn = ops.emb_bwd_ftrl_wide if wide_table else ops.emb_bwd_ftrl
+        return lambda: fn(tbl, *sts, ids, g, lr=LR, l1=L1, l2=L2,
+                          workspace=workspace)
 
     record("sgd_fused_wide", lambda: C.emb_bwd_sgd_fused_wide(
         table, wide, ids, grad, gw, LR, 1.0))
-    record("adagrad_pass1_accumulate", lambda: C.emb_bwd_sgd_fused_wide(
+    record(f"{tag}_pass1_accumulate", lambda: C.emb_bwd_sgd_fused_wide(
         ws.acc, ws.wide_acc, ids, grad, gw, -1.0, 1.0))
     # consumes the accumulated sums once, then runs on a clean
     # accumulator: same claims and row traffic every call
-    record("adagrad_pass2_claim_apply",
-           lambda: C.sparse_adagrad_apply_fused_wide(
-               table, state, ws.acc, wide, wide_state, ws.wide_acc,
-               ws.stamp, ids, ws.next_epoch(), LR, EPS))
+    record(f"{tag}_pass2_claim_apply", pass2)
     assert not ws.acc.any() and not ws.wide_acc.any()
-    record("adagrad_fused_wide_total",
-           lambda: ops.emb_bwd_adagrad_fused_wide(
-               table, state, wide, wide_state, ids, grad, gw, lr=LR,
-               eps=EPS, workspace=ws))
-    record("adagrad_deep_only", lambda: ops.emb_bwd_adagrad(
-        table, state, ids, grad, lr=LR, eps=EPS, workspace=ws))
-    record("adagrad_wide_only", lambda: ops.emb_bwd_adagrad_wide(
-        wide, wide_state, ids, gw, lr=LR, eps=EPS,
-        workspace=ws.wide_view()))
+    record(f"{tag}_fused_wide_total", total)
+    record(f"{tag}_deep_only",
+           single(rules[0], table, states, grad, ws, False))
+    record(f"{tag}_wide_only",
+           single(rules[1], wide, wide_states, gw, ws.wide_view(), True))
     record("torch_unique_index_add", lambda: torch_baseline(
-        table, state, wide, wide_state, ids, grad, gw))
+        rules, table, states, wide, wide_states, ids, grad, gw))
 
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)),

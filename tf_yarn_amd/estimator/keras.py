@@ -24,11 +24,12 @@ def _resolve_optimizer(opt, params):
     if isinstance(opt, str):
         name = opt.lower()
         from tf_yarn_amd.ops.optim import (FusedAdadelta, FusedAdagrad,
-                                           FusedAdam, FusedSGD)
+                                           FusedAdam, FusedFtrl, FusedSGD)
         table = {
             "sgd": lambda p: FusedSGD(p, lr=0.01),
             "adam": lambda p: FusedAdam(p, lr=1e-3),
             "adagrad": lambda p: FusedAdagrad(p, lr=0.01),
+            "ftrl": lambda p: FusedFtrl(p, lr=0.001),
             "adadelta": lambda p: FusedAdadelta(p, lr=1.0),
         }
         if name not in table:

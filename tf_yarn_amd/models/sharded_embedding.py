@@ -294,10 +294,15 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
     fills ``deep_out_buf[:, col_offset:]`` with [B, F*D] (owner-permuted
     feature order, consistent across steps) and returns the wide sums [B].
 
-    ``sparse_optimizer="adagrad"`` makes the owner-local update sparse
-    Adagrad (``state_sum`` / ``wide_state_sum`` buffers, per rank like the
-    tables).  The binned scatter and its forward-time permutation
-    prefetch are SGD-only and are skipped under Adagrad.
+    ``sparse_optimizer`` / ``wide_sparse_optimizer`` (None: the same)
+    pick the owner-local update rule per table: ``"adagrad"`` keeps
+    ``state_sum`` / ``wide_state_sum``, ``"ftrl"`` keeps ``ftrl_accum`` +
+    ``ftrl_linear`` / ``wide_ftrl_accum`` + ``wide_ftrl_linear`` (per rank
+    like the tables; a table owns state for its own rule only).
+    ``sparse_l1`` / ``sparse_l2`` regularise FTRL, ``wide_sparse_lr``
+    fixes the wide table's lr.  The binned scatter and its forward-time
+    permutation prefetch are SGD-only and run only when both tables are
+    ``"sgd"``.
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
@@ -305,7 +310,10 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                  init_std: Optional[float] = None,
                  wide_init_std: float = 0.01,
                  sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
-                 sparse_initial_accumulator: float = 0.0):
+                 sparse_initial_accumulator: float = 0.0,
+                 wide_sparse_optimizer: Optional[str] = None,
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0,
+                 wide_sparse_lr: Optional[float] = None):
         super().__init__()
         import math
         self.F = len(table_sizes)
@@ -328,9 +336,16 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             torch.randn(total_own, 1) * wide_init_std)
         self.wide_weight._miyarn_sparse = True
         self.wide_weight._miyarn_sharded = True
+        if wide_sparse_optimizer is None:
+            wide_sparse_optimizer = sparse_optimizer
+        self.sparse_optimizer = sparse_optimizer
+        self.wide_sparse_optimizer = wide_sparse_optimizer
         self._init_sparse_optimizer(
-            sparse_optimizer, sparse_eps, sparse_initial_accumulator,
-            {"state_sum": self.weight, "wide_state_sum": self.wide_weight})
+            sparse_eps, sparse_initial_accumulator,
+            {"": (self.weight, sparse_optimizer),
+             "wide_": (self.wide_weight, wide_sparse_optimizer)},
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2,
+            wide_sparse_lr=wide_sparse_lr)
         offs = torch.tensor(
             [0] + list(torch.cumsum(torch.tensor(own_sizes), 0)[:-1]),
             dtype=torch.int64)
@@ -408,7 +423,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         stream DURING FORWARD: it depends only on the ids, and its
         ~200 us of latency/atomic-bound work hides under the MFMA-bound
         MLP GEMMs instead of sitting on the backward critical path."""
-        if self.sparse_optimizer != "sgd":
+        if self._stateful():
             return  # the binned scatter is an SGD kernel
         if not (flat_ids.is_cuda and self.dim == 16 and ops.HAVE_EXT
                 and torch.is_grad_enabled() and self._binned_on(flat_ids)):
@@ -451,46 +466,101 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                 "binned-dedup" if self._binned_auto else "atomic")
         return self._binned_auto
 
-    def _apply_pending_adagrad(self, lr: float) -> None:
-        """Sparse Adagrad on the owner-local tables.  Deep and wide sink
-        entries that share their flat ids take the fused deep+wide entry
-        (ids read once per pass, one claim per row for both tables), as
-        the SGD path does; the binned scatter is never used here."""
+    def _stateful(self) -> bool:
+        return (self.sparse_optimizer, self.wide_sparse_optimizer) != \
+            ("sgd", "sgd")
+
+    # rule pairs (deep, wide) that have a fused deep+wide entry point
+    _FUSED_PAIRS = (("adagrad", "adagrad"), ("adagrad", "ftrl"),
+                    ("ftrl", "ftrl"))
+
+    def _apply_fused_pair(self, flat_ids, grad2d, gw, lr: float,
+                          wide_lr: float, scale: float, ws) -> None:
+        pair = (self.sparse_optimizer, self.wide_sparse_optimizer)
+        deep, wide = self.weight.data, self.wide_weight.data
+        if pair == ("adagrad", "adagrad") and wide_lr == lr:
+            ops.emb_bwd_adagrad_fused_wide(
+                deep, self.state_sum, wide, self.wide_state_sum, flat_ids,
+                grad2d, gw, lr=lr, eps=self.sparse_eps, scale=scale,
+                workspace=ws)
+        elif pair == ("adagrad", "ftrl"):
+            ops.emb_bwd_adagrad_ftrl_fused_wide(
+                deep, self.state_sum, wide, self.wide_ftrl_accum,
+                self.wide_ftrl_linear, flat_ids, grad2d, gw, lr=lr,
+                eps=self.sparse_eps, wide_lr=wide_lr, l1=self.sparse_l1,
+                l2=self.sparse_l2, scale=scale, workspace=ws)
+        elif pair == ("ftrl", "ftrl"):
+            ops.emb_bwd_ftrl_fused_wide(
+                deep, self.ftrl_accum, self.ftrl_linear, wide,
+                self.wide_ftrl_accum, self.wide_ftrl_linear, flat_ids,
+                grad2d, gw, lr=lr, wide_lr=wide_lr, l1=self.sparse_l1,
+                l2=self.sparse_l2, scale=scale, workspace=ws)
+        else:  # Adagrad pair at two rates: the fused kernel has one lr
+            self._sparse_apply_one(self.sparse_optimizer, "", deep,
+                                   flat_ids, grad2d, lr, scale, ws,
+                                   wide=False)
+            self._sparse_apply_one(self.wide_sparse_optimizer, "wide_",
+                                   wide, flat_ids, gw, wide_lr, scale,
+                                   ws.wide_view(), wide=True)
+
+    def _apply_pending_stateful(self, lr: float) -> None:
+        """Owner-local update when at least one table has a stateful rule
+        (Adagrad, FTRL).  Deep and wide sink entries that share their
+        flat ids take the fused deep+wide entry of their rule pair (ids
+        read once per pass, one claim per row for both tables), as the
+        SGD path does; everything else, pairs with SGD on one side
+        included, takes single-table calls.  The binned scatter is never
+        used here."""
         scale = 1.0 / self.world
-        ws = self._adagrad_workspace(self.weight.data,
-                                     self.wide_weight.data)
+        deep_rule, wide_rule = (self.sparse_optimizer,
+                                self.wide_sparse_optimizer)
+        wide_lr = lr if self.wide_sparse_lr is None else self.wide_sparse_lr
+        deep, wide = self.weight.data, self.wide_weight.data
+        if deep_rule == "sgd":
+            deep_ws, wide_ws = None, self._adagrad_workspace(wide)
+        elif wide_rule == "sgd":
+            deep_ws, wide_ws = self._adagrad_workspace(deep), None
+        else:
+            deep_ws = self._adagrad_workspace(deep, wide)
+            wide_ws = deep_ws.wide_view()
+        fusable = (deep_rule, wide_rule) in self._FUSED_PAIRS
         wide_by_ids = {gw_ids.data_ptr(): (i, gw)
                        for i, (gw_ids, gw) in enumerate(self._wide_sink)}
         fused_wide_done = set()
         for flat_ids, grad in self._deep_sink:
             grad2d = grad.reshape(flat_ids.numel(), self.dim)
             mate = wide_by_ids.get(flat_ids.data_ptr())
-            if mate is not None and mate[0] not in fused_wide_done:
-                ops.emb_bwd_adagrad_fused_wide(
-                    self.weight.data, self.state_sum,
-                    self.wide_weight.data, self.wide_state_sum, flat_ids,
-                    grad2d, mate[1], lr=lr, eps=self.sparse_eps,
-                    scale=scale, workspace=ws)
+            if (fusable and mate is not None
+                    and mate[0] not in fused_wide_done):
+                self._apply_fused_pair(flat_ids, grad2d, mate[1], lr,
+                                       wide_lr, scale, deep_ws)
                 fused_wide_done.add(mate[0])
+            elif deep_rule == "sgd":
+                ops.emb_bwd_sgd(deep, flat_ids, grad2d, lr=lr, scale=scale)
             else:
-                ops.emb_bwd_adagrad(
-                    self.weight.data, self.state_sum, flat_ids, grad2d,
-                    lr=lr, eps=self.sparse_eps, scale=scale, workspace=ws)
+                self._sparse_apply_one(deep_rule, "", deep, flat_ids,
+                                       grad2d, lr, scale, deep_ws,
+                                       wide=False)
         self._deep_sink.clear()
         for i, (flat_ids, gw) in enumerate(self._wide_sink):
             if i in fused_wide_done:
                 continue
-            ops.emb_bwd_adagrad_wide(
-                self.wide_weight.data, self.wide_state_sum, flat_ids, gw,
-                lr=lr, eps=self.sparse_eps, scale=scale,
-                workspace=ws.wide_view())
+            if wide_rule == "sgd":
+                fan = self.F if self.world == 1 else self.f_own
+                ops.emb_scatter_sum(wide, flat_ids.reshape(gw.numel(), fan),
+                                    gw, alpha=-wide_lr * scale)
+            else:
+                self._sparse_apply_one(wide_rule, "wide_", wide, flat_ids,
+                                       gw, wide_lr, scale, wide_ws,
+                                       wide=True)
         self._wide_sink.clear()
 
     def _apply_pending(self, lr: float) -> None:
-        if self.sparse_optimizer == "adagrad":
-            self._apply_pending_adagrad(lr)
+        if self._stateful():
+            self._apply_pending_stateful(lr)
             return
         scale = 1.0 / self.world
+        wide_lr = lr if self.wide_sparse_lr is None else self.wide_sparse_lr
         # Binned scatter (round-2 kernel): one region-binned permutation
         # shared by the deep and wide updates (identical flat ids), LDS
         # dedup + exclusive-owner writeback instead of 27M random global
@@ -535,7 +605,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             key = flat_ids.data_ptr()
             mate = wide_by_ids.get(key)
             if (mate is not None and flat_ids.is_cuda and ops.HAVE_EXT
-                    and self.dim % 4 == 0
+                    and self.dim % 4 == 0 and wide_lr == lr
                     and grad2d.dtype == mate[1].dtype
                     and mate[0] not in fused_wide_done):
                 ops.emb_bwd_sgd_fused_wide(
@@ -553,12 +623,12 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             if use_binned:
                 ops.emb_scatter_sum_binned(
                     self.wide_weight.data, flat_ids, gw,
-                    alpha=-lr * scale, perm=perm_for(flat_ids))
+                    alpha=-wide_lr * scale, perm=perm_for(flat_ids))
                 continue
             fan = self.F if self.world == 1 else self.f_own
             ids2d = flat_ids.reshape(gw.numel(), fan)
             ops.emb_scatter_sum(self.wide_weight.data, ids2d, gw,
-                                alpha=-lr * scale)
+                                alpha=-wide_lr * scale)
         self._wide_sink.clear()
 
     def clear_pending(self) -> None:

@@ -40,55 +40,106 @@ CRITEO_SPARSE = 26
 DEFAULT_TABLE_SIZES = [1_000_000] * CRITEO_SPARSE
 
 
-SPARSE_OPTIMIZERS = ("sgd", "adagrad")
+SPARSE_OPTIMIZERS = ("sgd", "adagrad", "ftrl")
+
+
+def _check_sparse_rule(name: str, value: str) -> str:
+    if value not in SPARSE_OPTIMIZERS:
+        raise ValueError(
+            f"{name} must be one of {SPARSE_OPTIMIZERS}, got {value!r}")
+    return value
 
 
 class SparseOptimizerMixin:
     """Per-table sparse-optimizer choice for the embedding modules.
 
-    The sparse optimizer is chosen ON THE MODEL (``sparse_optimizer=``),
-    never inferred from the dense optimizer; ``apply_sparse_updates(lr)``
-    keeps its signature and branches on the mode.  ``"sgd"`` (default)
-    adds no attribute that shows in ``state_dict``, no memory and no
-    kernel.  ``"adagrad"`` adds, per table:
+    The sparse optimizer is chosen ON THE MODEL (``sparse_optimizer=``,
+    and ``wide_sparse_optimizer=`` where a module also owns the wide
+    table), never inferred from the dense optimizer;
+    ``apply_sparse_updates(lr)`` keeps its signature and branches on the
+    rule.  ``"sgd"`` (default) adds no attribute that shows in
+    ``state_dict``, no memory and no kernel.  A stateful rule adds, per
+    table that uses it (``<p>`` is ``""`` or ``"wide_"``):
 
-    * ``<state name>``: persistent fp32 buffer shaped like the table,
-      filled with ``sparse_initial_accumulator`` (checkpoints carry it);
+    * ``"adagrad"``: ``<p>state_sum``; ``"ftrl"``: ``<p>ftrl_accum`` and
+      ``<p>ftrl_linear`` — persistent fp32 buffers shaped like the table
+      (checkpoints carry them).  ``state_sum`` and ``ftrl_accum`` start at
+      ``sparse_initial_accumulator``, ``ftrl_linear`` at 0.  A table owns
+      state for its own rule only;
     * a non-persistent accumulator + int32 row stamp, allocated on the
-      first apply (:class:`tf_yarn_amd.ops.SparseAdagradWorkspace`).
+      first apply (:class:`tf_yarn_amd.ops.SparseWorkspace`, shared by
+      the pair whatever their rules).
 
     All of them are flagged ``_miyarn_sharded`` in every mode so
     ``BucketedDataParallel`` never re-broadcasts a table-sized buffer per
     forward; replicated tables stay consistent because every rank applies
     the same allgathered updates."""
 
-    def _init_sparse_optimizer(self, sparse_optimizer: str,
-                               sparse_eps: float,
+    def _init_sparse_optimizer(self, sparse_eps: float,
                                sparse_initial_accumulator: float,
-                               states: dict) -> None:
-        """``states``: state buffer name -> the table parameter it
-        follows; the first entry owns the row stamp."""
-        if sparse_optimizer not in SPARSE_OPTIMIZERS:
+                               tables: dict, sparse_l1: float = 0.0,
+                               sparse_l2: float = 0.0,
+                               wide_sparse_lr: Optional[float] = None
+                               ) -> None:
+        """``tables``: state-name prefix -> (table parameter, rule), deep
+        table first; the first stateful entry owns the row stamp."""
+        for prefix, (_, rule) in tables.items():
+            _check_sparse_rule(f"{prefix}sparse_optimizer", rule)
+        if not (sparse_l1 >= 0 and sparse_l2 >= 0):
+            raise ValueError("sparse_l1 and sparse_l2 must be >= 0, got "
+                             f"{sparse_l1!r}, {sparse_l2!r}")
+        if wide_sparse_lr is not None and not wide_sparse_lr > 0:
             raise ValueError(
-                f"sparse_optimizer must be one of {SPARSE_OPTIMIZERS}, "
-                f"got {sparse_optimizer!r}")
-        self.sparse_optimizer = sparse_optimizer
+                f"wide_sparse_lr must be > 0, got {wide_sparse_lr!r}")
         self.sparse_eps = float(sparse_eps)
+        self.sparse_l1 = float(sparse_l1)
+        self.sparse_l2 = float(sparse_l2)
+        self.wide_sparse_lr = (None if wide_sparse_lr is None
+                               else float(wide_sparse_lr))
         self._sparse_buffer_names: List[str] = []
-        self._sparse_ws: Optional[ops.SparseAdagradWorkspace] = None
-        if sparse_optimizer != "adagrad":
-            return
-        for i, (name, table) in enumerate(states.items()):
-            self.register_buffer(
-                name, torch.full_like(table.detach(),
-                                      float(sparse_initial_accumulator)),
-                persistent=True)
-            acc = "_adagrad_acc" if i == 0 else f"_adagrad_acc{i}"
+        self._sparse_ws: Optional[ops.SparseWorkspace] = None
+        init = float(sparse_initial_accumulator)
+        n_stateful = 0
+        for prefix, (table, rule) in tables.items():
+            if rule == "sgd":
+                continue
+            if rule == "adagrad":
+                fills = {prefix + "state_sum": init}
+            else:
+                fills = {prefix + "ftrl_accum": init,
+                         prefix + "ftrl_linear": 0.0}
+            for name, value in fills.items():
+                self.register_buffer(
+                    name, torch.full_like(table.detach(), value),
+                    persistent=True)
+            acc = ("_adagrad_acc" if n_stateful == 0
+                   else f"_adagrad_acc{n_stateful}")
             self.register_buffer(acc, None, persistent=False)
-            self._sparse_buffer_names += [name, acc]
+            self._sparse_buffer_names += list(fills) + [acc]
+            n_stateful += 1
+        if n_stateful == 0:
+            return
         self.register_buffer("_adagrad_stamp", None, persistent=False)
         self._sparse_buffer_names.append("_adagrad_stamp")
         self._flag_sparse_buffers()
+
+    def _sparse_apply_one(self, rule: str, prefix: str,
+                          table: torch.Tensor, ids: torch.Tensor,
+                          grad: torch.Tensor, lr: float, scale: float,
+                          workspace, wide: bool) -> None:
+        """One single-table stateful update (``rule`` is not "sgd") with
+        this module's state buffers ``<prefix>...``."""
+        if rule == "adagrad":
+            fn = ops.emb_bwd_adagrad_wide if wide else ops.emb_bwd_adagrad
+            fn(table, getattr(self, prefix + "state_sum"), ids, grad,
+               lr=lr, eps=self.sparse_eps, scale=scale,
+               workspace=workspace)
+            return
+        fn = ops.emb_bwd_ftrl_wide if wide else ops.emb_bwd_ftrl
+        fn(table, getattr(self, prefix + "ftrl_accum"),
+           getattr(self, prefix + "ftrl_linear"), ids, grad, lr=lr,
+           l1=self.sparse_l1, l2=self.sparse_l2, scale=scale,
+           workspace=workspace)
 
     def _flag_sparse_buffers(self) -> None:
         for name in getattr(self, "_sparse_buffer_names", ()):
@@ -162,13 +213,16 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
     After ``loss.backward()`` call :meth:`apply_sparse_updates` (the
     training loop or the framework optimizer wrapper does this).
     ``sparse_optimizer="adagrad"`` replaces the scatter+SGD update with
-    sparse Adagrad (state in the ``state_sum`` buffer).
+    sparse Adagrad (state in the ``state_sum`` buffer), ``"ftrl"`` with
+    sparse FTRL-proximal (``ftrl_accum`` / ``ftrl_linear``, regularised
+    by ``sparse_l1`` / ``sparse_l2``).
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
                  out_bf16: bool = False, init_std: Optional[float] = None,
                  sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
-                 sparse_initial_accumulator: float = 0.0):
+                 sparse_initial_accumulator: float = 0.0,
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.dim = dim
@@ -182,9 +236,12 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         weight = torch.randn(total, dim) * std
         self.weight = nn.Parameter(weight)
         self.weight._miyarn_sparse = True  # dense reducer must skip it
-        self._init_sparse_optimizer(sparse_optimizer, sparse_eps,
-                                    sparse_initial_accumulator,
-                                    {"state_sum": self.weight})
+        self.sparse_optimizer = _check_sparse_rule("sparse_optimizer",
+                                                   sparse_optimizer)
+        self._init_sparse_optimizer(
+            sparse_eps, sparse_initial_accumulator,
+            {"": (self.weight, sparse_optimizer)},
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -236,11 +293,11 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         for all_ids, all_grads, works in getattr(self, "_gathered", []):
             for w in works:
                 w.wait()
-            if self.sparse_optimizer == "adagrad":
-                ops.emb_bwd_adagrad(
-                    self.weight.data, self.state_sum, all_ids, all_grads,
-                    lr=lr, eps=self.sparse_eps, scale=1.0 / world,
-                    workspace=self._adagrad_workspace(self.weight.data))
+            if self.sparse_optimizer != "sgd":
+                self._sparse_apply_one(
+                    self.sparse_optimizer, "", self.weight.data, all_ids,
+                    all_grads, lr, 1.0 / world,
+                    self._adagrad_workspace(self.weight.data), wide=False)
                 continue
             ops.emb_bwd_sgd(self.weight.data, all_ids, all_grads,
                             lr=lr, scale=1.0 / world)
@@ -283,12 +340,16 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
     """Per-id scalar weights with fused gather-sum forward and
     scatter-add sparse update (the wide part of wide-and-deep);
     ``sparse_optimizer="adagrad"`` switches the update to sparse
-    Adagrad."""
+    Adagrad, ``"ftrl"`` to sparse FTRL-proximal (the canonical rule for
+    this table; ``sparse_l1 > 0`` leaves exact zeros).  ``wide_sparse_lr``
+    fixes this table's lr whatever ``apply_sparse_updates`` is given."""
 
     def __init__(self, table_sizes: List[int], out_bf16: bool = False,
                  init_std: float = 0.01, sparse_optimizer: str = "sgd",
                  sparse_eps: float = 1e-10,
-                 sparse_initial_accumulator: float = 0.0):
+                 sparse_initial_accumulator: float = 0.0,
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0,
+                 wide_sparse_lr: Optional[float] = None):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.out_bf16 = out_bf16
@@ -299,9 +360,13 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
         self.register_buffer("offsets", offsets, persistent=True)
         self.weight = nn.Parameter(torch.randn(total, 1) * init_std)
         self.weight._miyarn_sparse = True
-        self._init_sparse_optimizer(sparse_optimizer, sparse_eps,
-                                    sparse_initial_accumulator,
-                                    {"state_sum": self.weight})
+        self.sparse_optimizer = _check_sparse_rule("sparse_optimizer",
+                                                   sparse_optimizer)
+        self._init_sparse_optimizer(
+            sparse_eps, sparse_initial_accumulator,
+            {"": (self.weight, sparse_optimizer)},
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2,
+            wide_sparse_lr=wide_sparse_lr)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -344,14 +409,16 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
     @torch.no_grad()
     def finish_sparse_sync(self, lr: float) -> None:
         world = getattr(self, "_pending_world", 1)
+        if self.wide_sparse_lr is not None:
+            lr = self.wide_sparse_lr
         for all_ids, all_grads, works in getattr(self, "_gathered", []):
             for w in works:
                 w.wait()
-            if self.sparse_optimizer == "adagrad":
-                ops.emb_bwd_adagrad_wide(
-                    self.weight.data, self.state_sum, all_ids, all_grads,
-                    lr=lr, eps=self.sparse_eps, scale=1.0 / world,
-                    workspace=self._adagrad_workspace(self.weight.data))
+            if self.sparse_optimizer != "sgd":
+                self._sparse_apply_one(
+                    self.sparse_optimizer, "", self.weight.data, all_ids,
+                    all_grads, lr, 1.0 / world,
+                    self._adagrad_workspace(self.weight.data), wide=True)
                 continue
             ops.emb_scatter_sum(self.weight.data,
                                 all_ids.reshape(all_grads.numel(), -1),
@@ -460,17 +527,34 @@ class WideAndDeep(nn.Module):
                  process_group=None,
                  sparse_optimizer: str = "sgd",
                  sparse_eps: float = 1e-10,
-                 sparse_initial_accumulator: float = 0.0):
-        """``sparse_optimizer`` ("sgd" or "adagrad") picks the update rule
-        of the embedding tables; it is NOT inferred from the dense
-        optimizer, whose lr is what ``apply_sparse_updates(lr)``
-        receives."""
+                 sparse_initial_accumulator: float = 0.0,
+                 wide_sparse_optimizer: Optional[str] = None,
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0,
+                 wide_sparse_lr: Optional[float] = None):
+        """``sparse_optimizer`` ("sgd", "adagrad" or "ftrl") picks the
+        update rule of the embedding tables; it is NOT inferred from the
+        dense optimizer, whose lr is what ``apply_sparse_updates(lr)``
+        receives.  ``wide_sparse_optimizer`` picks the wide table's rule
+        (None: the same as ``sparse_optimizer``), so the textbook
+        wide-and-deep recipe is ``sparse_optimizer="adagrad",
+        wide_sparse_optimizer="ftrl", sparse_l1=...``.
+
+        ``sparse_l1`` / ``sparse_l2``: FTRL's regularisation strengths
+        (L1 > 0 is what makes untrained-away weights exactly 0).
+        ``wide_sparse_lr``: when set, the wide table runs at this fixed
+        lr instead of the one passed to ``apply_sparse_updates``.
+        ``sparse_initial_accumulator`` fills Adagrad's ``state_sum`` and
+        FTRL's ``ftrl_accum`` alike; TF's default for both is 0.1."""
         super().__init__()
         table_sizes = table_sizes or DEFAULT_TABLE_SIZES
+        if wide_sparse_optimizer is None:
+            wide_sparse_optimizer = sparse_optimizer
         sparse_kw = dict(
             sparse_optimizer=sparse_optimizer, sparse_eps=sparse_eps,
-            sparse_initial_accumulator=sparse_initial_accumulator)
+            sparse_initial_accumulator=sparse_initial_accumulator,
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2)
         self.sparse_optimizer = sparse_optimizer
+        self.wide_sparse_optimizer = wide_sparse_optimizer
         self.compute_dtype = compute_dtype
         self.dense_dim = dense_dim
         bf16 = compute_dtype == torch.bfloat16
@@ -480,7 +564,9 @@ class WideAndDeep(nn.Module):
                 ShardedCriteoEmbeddings
             self.embeddings = ShardedCriteoEmbeddings(
                 table_sizes, embedding_dim, out_bf16=bf16,
-                process_group=process_group, **sparse_kw)
+                process_group=process_group,
+                wide_sparse_optimizer=wide_sparse_optimizer,
+                wide_sparse_lr=wide_sparse_lr, **sparse_kw)
             self.deep_embedding = None
             self.wide_embedding = None
         else:
@@ -488,9 +574,11 @@ class WideAndDeep(nn.Module):
             self.deep_embedding = SparseEmbedding(
                 table_sizes, embedding_dim, out_bf16=bf16, **sparse_kw)
             # Wide: one scalar weight per categorical id
+            wide_kw = dict(sparse_kw, sparse_optimizer=wide_sparse_optimizer,
+                           wide_sparse_lr=wide_sparse_lr)
             self.wide_embedding = WideScalarEmbedding(table_sizes,
                                                       out_bf16=bf16,
-                                                      **sparse_kw)
+                                                      **wide_kw)
         self.wide_dense = ScalarHead(dense_dim, compute_dtype)
         layers: List[nn.Module] = []
         # dense block padded to 16 columns for quad-aligned fused gather
@@ -580,7 +668,11 @@ class FlatInputWideAndDeep(nn.Module):
                  compute_dtype: torch.dtype = torch.float32,
                  sharded: bool = False, process_group=None,
                  sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
-                 sparse_initial_accumulator: float = 0.0):
+                 sparse_initial_accumulator: float = 0.0,
+                 wide_sparse_optimizer: Optional[str] = None,
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0,
+                 wide_sparse_lr: Optional[float] = None):
+        """The sparse-optimizer arguments are :class:`WideAndDeep`'s."""
         super().__init__()
         self.dense_dim = dense_dim
         init_acc = sparse_initial_accumulator
@@ -588,6 +680,9 @@ class FlatInputWideAndDeep(nn.Module):
                                sparse_optimizer=sparse_optimizer,
                                sparse_eps=sparse_eps,
                                sparse_initial_accumulator=init_acc,
+                               wide_sparse_optimizer=wide_sparse_optimizer,
+                               sparse_l1=sparse_l1, sparse_l2=sparse_l2,
+                               wide_sparse_lr=wide_sparse_lr,
                                table_sizes=table_sizes,
                                embedding_dim=embedding_dim, hidden=hidden,
                                compute_dtype=compute_dtype,

@@ -131,6 +131,50 @@ def fused_adagrad(param: torch.Tensor, grad: torch.Tensor,
     param.addcdiv_(g, state_sum.sqrt().add_(eps), value=-lr)
 
 
+def _check_ftrl_args(lr: float, l1: float, l2: float) -> None:
+    if not lr > 0:
+        raise ValueError(f"FTRL needs lr > 0, got {lr!r}")
+    if not (l1 >= 0 and l2 >= 0):
+        raise ValueError(
+            f"FTRL needs l1 >= 0 and l2 >= 0, got l1={l1!r}, l2={l2!r}")
+
+
+def _ftrl_rule(g: torch.Tensor, n: torch.Tensor, z: torch.Tensor,
+               w: torch.Tensor, lr: float, l1: float, l2: float):
+    """FTRL-proximal (TF ``Ftrl``, ``learning_rate_power=-0.5``, no beta,
+    no L2 shrinkage) on same-shaped tensors; returns ``(n', z', w')``.
+    ``w'`` is exactly 0 where ``|z'| <= l1`` (which also covers q == 0:
+    that needs n' == 0 and l2 == 0, where z' == z == 0)."""
+    n_new = n + g * g
+    r_new = n_new.sqrt()
+    z_new = z + g - (r_new - n.sqrt()) / lr * w
+    q = r_new / lr + 2.0 * l2
+    w_new = torch.where(z_new.abs() > l1,
+                        (torch.sign(z_new) * l1 - z_new) / q,
+                        torch.zeros_like(z_new))
+    return n_new, z_new, w_new
+
+
+def fused_ftrl(param: torch.Tensor, grad: torch.Tensor,
+               accum: torch.Tensor, linear: torch.Tensor, *, lr: float,
+               l1: float = 0.0, l2: float = 0.0,
+               grad_scale: float = 1.0) -> None:
+    """Dense FTRL-proximal step: EVERY element is recomputed from
+    ``(linear, accum)`` every step (TF's dense semantics; the sparse
+    tables use :func:`emb_bwd_ftrl`, which only touches the batch's
+    rows)."""
+    _check_ftrl_args(lr, l1, l2)
+    if _on_gpu(param, grad):
+        _require_ext()
+        _C.fused_ftrl(param, grad, accum, linear, lr, l1, l2, grad_scale)
+        return
+    g = grad.float() * grad_scale
+    n, z, w = _ftrl_rule(g, accum, linear, param, lr, l1, l2)
+    accum.copy_(n)
+    linear.copy_(z)
+    param.copy_(w)
+
+
 def fused_adadelta(param: torch.Tensor, grad: torch.Tensor,
                    square_avg: torch.Tensor, acc_delta: torch.Tensor,
                    *, lr: float = 1.0, rho: float = 0.9, eps: float = 1e-6,
@@ -451,6 +495,171 @@ def emb_bwd_adagrad_fused_wide(table: torch.Tensor, state_sum: torch.Tensor,
                     scale=scale)
     emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
                          eps=eps, scale=scale)
+
+
+# ---- sparse FTRL -----------------------------------------------------------
+
+# The workspace holds no rule state (accumulator + stamp + epoch): one
+# instance, and so one stamp, serves a deep Adagrad table and its wide
+# FTRL companion.
+SparseWorkspace = SparseAdagradWorkspace
+
+
+def _ftrl_rows_ref(table: torch.Tensor, accum: torch.Tensor,
+                   linear: torch.Tensor, flat_ids: torch.Tensor,
+                   rows: torch.Tensor, lr: float, l1: float, l2: float,
+                   scale: float) -> None:
+    """Reference: coalesce duplicate ids, then one FTRL step on the unique
+    rows ONLY (lazy semantics: a dense step would recompute every weight
+    from (z, n) and wipe the initial weights of untouched rows)."""
+    uniq, inv = torch.unique(flat_ids, return_inverse=True)
+    g = torch.zeros(uniq.numel(), rows.shape[1], dtype=torch.float32,
+                    device=rows.device)
+    g.index_add_(0, inv, rows.float())
+    g.mul_(scale)
+    n, z, w = _ftrl_rule(g, accum.index_select(0, uniq),
+                         linear.index_select(0, uniq),
+                         table.index_select(0, uniq), lr, l1, l2)
+    accum.index_copy_(0, uniq, n)
+    linear.index_copy_(0, uniq, z)
+    table.index_copy_(0, uniq, w)
+
+
+def _fused_pair_covers(table: torch.Tensor, grad: torch.Tensor,
+                       gw: torch.Tensor) -> bool:
+    """Shapes the fused deep+wide kernels take: ``dim/4`` a power of two
+    <= 64 and one gradient dtype."""
+    dvec, rem = divmod(table.shape[1], 4)
+    return (rem == 0 and 1 <= dvec <= 64 and dvec & (dvec - 1) == 0
+            and grad.dtype == gw.dtype)
+
+
+def emb_bwd_ftrl(table: torch.Tensor, accum: torch.Tensor,
+                 linear: torch.Tensor, ids: torch.Tensor,
+                 grad: torch.Tensor, *, lr: float, l1: float = 0.0,
+                 l2: float = 0.0, scale: float = 1.0,
+                 workspace: Optional[SparseWorkspace] = None) -> None:
+    """Sparse FTRL-proximal on the rows named by ``ids`` (TF ``Ftrl`` with
+    ``learning_rate_power=-0.5``, no beta, no L2 shrinkage).  For each
+    unique id u, ``G = scale * sum(grad[i] for ids[i] == u)`` and per
+    element, with ``n = accum[u]``, ``z = linear[u]``, ``w = table[u]``::
+
+        n' = n + G*G
+        z' = z + G - (sqrt(n') - sqrt(n)) / lr * w
+        w' = (sign(z') * l1 - z') / (sqrt(n') / lr + 2*l2)  if |z'| > l1
+             0.0                                             otherwise
+
+    Rows not in ``ids`` are neither read nor written (NOT a dense step
+    with zero gradients); a touched row whose gradients sum to 0 is still
+    recomputed from ``(z, n)``.  ``grad`` fp32 or bf16; table and both
+    states fp32, any ``dim >= 1``.
+
+    GPU: the accumulate-then-claim kernels of :func:`emb_bwd_adagrad`
+    with the FTRL rule (``csrc/sparse_adagrad.hip``)."""
+    _check_ftrl_args(lr, l1, l2)
+    flat = ids.reshape(-1)
+    if _on_gpu(table, accum, linear, ids, grad):
+        _require_ext()
+        ws = workspace if workspace is not None else SparseWorkspace(table)
+        _C.emb_bwd_ftrl(table, accum, linear, ws.acc, ws.stamp,
+                        flat.contiguous(), grad.contiguous(),
+                        ws.next_epoch(), lr, l1, l2, scale)
+        return
+    _ftrl_rows_ref(table, accum, linear, flat,
+                   grad.reshape(flat.numel(), -1), lr, l1, l2, scale)
+
+
+def emb_bwd_ftrl_wide(table: torch.Tensor, accum: torch.Tensor,
+                      linear: torch.Tensor, ids: torch.Tensor,
+                      gw: torch.Tensor, *, lr: float, l1: float = 0.0,
+                      l2: float = 0.0, scale: float = 1.0,
+                      workspace: Optional[SparseWorkspace] = None) -> None:
+    """:func:`emb_bwd_ftrl` for the ``[rows, 1]`` wide table, with the
+    ``gw[i // g_div]`` gradient layout of :func:`emb_bwd_adagrad_wide`."""
+    _check_ftrl_args(lr, l1, l2)
+    flat = ids.reshape(-1)
+    if _on_gpu(table, accum, linear, ids, gw):
+        _require_ext()
+        ws = workspace if workspace is not None else SparseWorkspace(table)
+        _C.emb_bwd_ftrl_wide(table, accum, linear, ws.acc, ws.stamp,
+                             flat.contiguous(), gw.reshape(-1).contiguous(),
+                             ws.next_epoch(), lr, l1, l2, scale)
+        return
+    if flat.numel() == 0:
+        return
+    g_div = flat.numel() // gw.numel()
+    rows = gw.float().reshape(-1, 1).expand(-1, g_div).reshape(-1, 1)
+    _ftrl_rows_ref(table.reshape(-1, 1), accum.reshape(-1, 1),
+                   linear.reshape(-1, 1), flat, rows, lr, l1, l2, scale)
+
+
+def emb_bwd_adagrad_ftrl_fused_wide(
+        table: torch.Tensor, state_sum: torch.Tensor,
+        wide_table: torch.Tensor, wide_accum: torch.Tensor,
+        wide_linear: torch.Tensor, ids: torch.Tensor, grad: torch.Tensor,
+        gw: torch.Tensor, *, lr: float, eps: float = 1e-10,
+        wide_lr: Optional[float] = None, l1: float = 0.0, l2: float = 0.0,
+        scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """The wide-and-deep recipe from the shared flat ids: sparse Adagrad
+    (``lr``, ``eps``) on the deep table and sparse FTRL (``wide_lr``,
+    default ``lr``; ``l1``, ``l2``) on the wide scalars, one claim per
+    row for both.  ``workspace`` must have been built with ``wide_table``.
+    Shapes the fused kernel does not cover take the two single-table ops
+    on the shared stamp, as in :func:`emb_bwd_adagrad_fused_wide`."""
+    wide_lr = lr if wide_lr is None else wide_lr
+    _check_ftrl_args(wide_lr, l1, l2)
+    ws = None
+    if _on_gpu(table, ids, grad, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseWorkspace(table, wide_table)
+        if _fused_pair_covers(table, grad, gw):
+            _C.emb_bwd_adagrad_ftrl_fused_wide(
+                table, state_sum, ws.acc, wide_table, wide_accum,
+                wide_linear, ws.wide_acc, ws.stamp,
+                ids.reshape(-1).contiguous(), grad.contiguous(),
+                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, eps,
+                wide_lr, l1, l2, scale)
+            return
+    emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
+                    scale=scale, workspace=ws)
+    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
+                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
+                      workspace=ws.wide_view() if ws is not None else None)
+
+
+def emb_bwd_ftrl_fused_wide(
+        table: torch.Tensor, accum: torch.Tensor, linear: torch.Tensor,
+        wide_table: torch.Tensor, wide_accum: torch.Tensor,
+        wide_linear: torch.Tensor, ids: torch.Tensor, grad: torch.Tensor,
+        gw: torch.Tensor, *, lr: float, wide_lr: Optional[float] = None,
+        l1: float = 0.0, l2: float = 0.0, scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """Sparse FTRL on BOTH CTR tables from the shared flat ids (``l1`` and
+    ``l2`` are shared; the wide table may run at its own ``wide_lr``).
+    Fallback rule as in :func:`emb_bwd_adagrad_ftrl_fused_wide`."""
+    wide_lr = lr if wide_lr is None else wide_lr
+    _check_ftrl_args(lr, l1, l2)
+    _check_ftrl_args(wide_lr, l1, l2)
+    ws = None
+    if _on_gpu(table, ids, grad, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseWorkspace(table, wide_table)
+        if _fused_pair_covers(table, grad, gw):
+            _C.emb_bwd_ftrl_fused_wide(
+                table, accum, linear, ws.acc, wide_table, wide_accum,
+                wide_linear, ws.wide_acc, ws.stamp,
+                ids.reshape(-1).contiguous(), grad.contiguous(),
+                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, wide_lr,
+                l1, l2, scale)
+            return
+    emb_bwd_ftrl(table, accum, linear, ids, grad, lr=lr, l1=l1, l2=l2,
+                 scale=scale, workspace=ws)
+    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
+                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
+                      workspace=ws.wide_view() if ws is not None else None)
 
 
 # ---- elementwise -----------------------------------------------------------

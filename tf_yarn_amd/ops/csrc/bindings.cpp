@@ -25,6 +25,9 @@ void fused_adam(torch::Tensor param, torch::Tensor grad,
 void fused_adagrad(torch::Tensor param, torch::Tensor grad,
                    torch::Tensor state_sum, double lr, double eps,
                    double weight_decay, double grad_scale);
+void fused_ftrl(torch::Tensor param, torch::Tensor grad,
+                torch::Tensor accum, torch::Tensor linear, double lr,
+                double l1, double l2, double grad_scale);
 void fused_adadelta(torch::Tensor param, torch::Tensor grad,
                     torch::Tensor square_avg, torch::Tensor acc_delta,
                     double lr, double rho, double eps, double weight_decay,
@@ -74,6 +77,45 @@ void emb_bwd_adagrad_fused_wide(
     torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
     torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
     double eps, double scale);
+void sparse_ftrl_apply(torch::Tensor table, torch::Tensor accum,
+                       torch::Tensor linear, torch::Tensor acc,
+                       torch::Tensor stamp, torch::Tensor ids,
+                       int64_t epoch, double lr, double l1, double l2);
+void sparse_adagrad_ftrl_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, int64_t epoch, double lr, double eps,
+    double wide_lr, double l1, double l2);
+void sparse_ftrl_apply_fused_wide(
+    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
+    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, int64_t epoch, double lr, double wide_lr, double l1,
+    double l2);
+void emb_bwd_ftrl(torch::Tensor table, torch::Tensor accum,
+                  torch::Tensor linear, torch::Tensor acc,
+                  torch::Tensor stamp, torch::Tensor ids,
+                  torch::Tensor grad, int64_t epoch, double lr, double l1,
+                  double l2, double scale);
+void emb_bwd_ftrl_wide(torch::Tensor table, torch::Tensor accum,
+                       torch::Tensor linear, torch::Tensor acc,
+                       torch::Tensor stamp, torch::Tensor ids,
+                       torch::Tensor gw, int64_t epoch, double lr,
+                       double l1, double l2, double scale);
+void emb_bwd_adagrad_ftrl_fused_wide(
+    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
+    double lr, double eps, double wide_lr, double l1, double l2,
+    double scale);
+void emb_bwd_ftrl_fused_wide(
+    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
+    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
+    double lr, double wide_lr, double l1, double l2, double scale);
 
 // binned_scatter.hip
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
@@ -149,6 +191,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Sparse Adagrad for the [rows, 1] wide table (gw[i / g_div])");
   m.def("emb_bwd_adagrad_fused_wide", &emb_bwd_adagrad_fused_wide,
         "Sparse Adagrad for the deep + wide pair (shared ids)");
+  m.def("sparse_ftrl_apply", &sparse_ftrl_apply,
+        "Sparse FTRL pass 2: claim each touched row once, consume the "
+        "accumulator, update accum + linear + table");
+  m.def("sparse_adagrad_ftrl_apply_fused_wide",
+        &sparse_adagrad_ftrl_apply_fused_wide,
+        "Pass 2 for a deep Adagrad + wide FTRL pair (shared ids)");
+  m.def("sparse_ftrl_apply_fused_wide", &sparse_ftrl_apply_fused_wide,
+        "Pass 2 for a deep FTRL + wide FTRL pair (shared ids)");
+  m.def("emb_bwd_ftrl", &emb_bwd_ftrl,
+        "Sparse FTRL-proximal: atomic accumulate + once-per-row "
+        "claim/apply");
+  m.def("emb_bwd_ftrl_wide", &emb_bwd_ftrl_wide,
+        "Sparse FTRL for the [rows, 1] wide table (gw[i / g_div])");
+  m.def("emb_bwd_adagrad_ftrl_fused_wide", &emb_bwd_adagrad_ftrl_fused_wide,
+        "Deep sparse Adagrad + wide sparse FTRL (shared ids)");
+  m.def("emb_bwd_ftrl_fused_wide", &emb_bwd_ftrl_fused_wide,
+        "Sparse FTRL for the deep + wide pair (shared ids)");
+  m.def("fused_ftrl", &fused_ftrl, "Fused dense FTRL-proximal step");
   m.def("bias_relu_fwd", &bias_relu_fwd, "Fused bias+ReLU forward");
   m.def("bias_relu_bwd", &bias_relu_bwd, "Fused ReLU backward");
   m.def("lt_linear", &lt_linear,

@@ -154,6 +154,51 @@ __global__ void adagrad_kernel(float* __restrict__ p,
   }
 }
 
+// Dense FTRL-proximal (TF Ftrl, learning_rate_power = -0.5, no beta, no L2
+// shrinkage): every element is recomputed from (z, n) every step.  The
+// rule is the one of the sparse tables (sparse_adagrad.hip, FtrlRule); q
+// can only be 0 where n' == 0 and l2 == 0, and there |z'| > l1 is false
+// for any state the rule itself produced, so the division is never reached.
+struct FtrlArgs { float lr, l1, l2, scale; };
+
+__device__ __forceinline__ void ftrl_one(float g, float* n, float* z,
+                                         float* w, FtrlArgs a) {
+  const float n_new = *n + g * g;
+  const float r_new = sqrtf(n_new);
+  const float zz = *z + g - (r_new - sqrtf(*n)) / a.lr * *w;
+  const float q = r_new / a.lr + 2.f * a.l2;
+  *n = n_new;
+  *z = zz;
+  *w = fabsf(zz) > a.l1 ? (copysignf(a.l1, zz) - zz) / q : 0.f;
+}
+
+template <typename GIo>
+__global__ void ftrl_kernel(float* __restrict__ p,
+                            const typename GIo::scalar_t* __restrict__ g,
+                            float* __restrict__ accum,
+                            float* __restrict__ linear,
+                            int64_t n, FtrlArgs a) {
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  const int64_t nvec = n >> 2;
+  for (int64_t i = tid; i < nvec; i += stride) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    f32x4 nv = reinterpret_cast<f32x4*>(accum)[i];
+    f32x4 zv = reinterpret_cast<f32x4*>(linear)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float nn = nv[j], zz = zv[j], ww = pv[j];
+      ftrl_one(GIo::load(g, i * 4 + j) * a.scale, &nn, &zz, &ww, a);
+      nv[j] = nn; zv[j] = zz; pv[j] = ww;
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(accum)[i] = nv;
+    reinterpret_cast<f32x4*>(linear)[i] = zv;
+  }
+  for (int64_t i = (nvec << 2) + tid; i < n; i += stride)
+    ftrl_one(GIo::load(g, i) * a.scale, &accum[i], &linear[i], &p[i], a);
+}
+
 struct AdadeltaArgs { float lr, rho, eps, weight_decay, scale; };
 
 template <typename GIo>
@@ -433,6 +478,33 @@ void fused_adagrad(torch::Tensor param, torch::Tensor grad,
                        0, stream, param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
                        state_sum.data_ptr<float>(), n, a);
+  }
+}
+
+void fused_ftrl(torch::Tensor param, torch::Tensor grad,
+                torch::Tensor accum, torch::Tensor linear, double lr,
+                double l1, double l2, double grad_scale) {
+  int64_t n = param.numel();
+  TORCH_CHECK(lr > 0.0, "FTRL needs lr > 0");
+  TORCH_CHECK(l1 >= 0.0 && l2 >= 0.0, "FTRL needs l1 >= 0 and l2 >= 0");
+  check_flat_f32(param, "param", n);
+  check_flat_f32(accum, "accum", n);
+  check_flat_f32(linear, "linear", n);
+  check_grad(grad, n);
+  FtrlArgs a{(float)lr, (float)l1, (float)l2, (float)grad_scale};
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  int grid = miyarn_grid((n + 3) / 4);
+  if (grad.scalar_type() == torch::kFloat32) {
+    hipLaunchKernelGGL(ftrl_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK),
+                       0, stream, param.data_ptr<float>(),
+                       grad.data_ptr<float>(), accum.data_ptr<float>(),
+                       linear.data_ptr<float>(), n, a);
+  } else {
+    hipLaunchKernelGGL(ftrl_kernel<Bf16Io>, dim3(grid), dim3(MIYARN_BLOCK),
+                       0, stream, param.data_ptr<float>(),
+                       reinterpret_cast<unsigned short*>(grad.data_ptr()),
+                       accum.data_ptr<float>(), linear.data_ptr<float>(),
+                       n, a);
   }
 }
 

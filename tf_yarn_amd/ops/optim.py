@@ -175,6 +175,53 @@ class FusedAdagrad(Optimizer):
         return loss
 
 
+class FusedFtrl(Optimizer):
+    """Dense FTRL-proximal (TF/Keras ``Ftrl`` with
+    ``learning_rate_power=-0.5``, no beta, no L2 shrinkage; Keras
+    defaults).  Every element is recomputed from its ``(linear, accum)``
+    state every step, so weights that start non-zero are replaced by the
+    FTRL solution on the first step, as in TF."""
+
+    def __init__(self, params: Iterable, lr: float = 1e-3,
+                 initial_accumulator_value: float = 0.1,
+                 l1: float = 0.0, l2: float = 0.0,
+                 grad_scale: float = 1.0):
+        if not lr > 0:
+            raise ValueError(f"lr must be > 0, got {lr!r}")
+        if not (l1 >= 0 and l2 >= 0):
+            raise ValueError(f"l1 and l2 must be >= 0, got {l1!r}, {l2!r}")
+        if initial_accumulator_value < 0:
+            raise ValueError("initial_accumulator_value must be >= 0")
+        defaults = dict(lr=lr, l1=l1, l2=l2, grad_scale=grad_scale,
+                        initial_accumulator_value=initial_accumulator_value)
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for group in self.param_groups:
+            for p in group["params"]:
+                if getattr(p, "_miyarn_sparse", False):
+                    continue
+                g = _grad_of(p)
+                if g is None:
+                    continue
+                state = self.state[p]
+                master, bf16 = _split_param(p, state)
+                if "accum" not in state:
+                    state["accum"] = torch.full_like(
+                        master, group["initial_accumulator_value"])
+                    state["linear"] = torch.zeros_like(master)
+                ops.fused_ftrl(
+                    _flat(master), _flat(g), _flat(state["accum"]),
+                    _flat(state["linear"]), lr=group["lr"],
+                    l1=group["l1"], l2=group["l2"],
+                    grad_scale=group["grad_scale"])
+                if bf16 is not None:
+                    bf16.copy_(master.to(torch.bfloat16))
+        return loss
+
+
 class FusedAdadelta(Optimizer):
     """Adadelta — the README's Keras example optimizer
     (reference README.md:106)."""

@@ -299,6 +299,22 @@ def make_adagrad_step(lr: float, eps: float = 1e-10) -> Callable:
     return step
 
 
+def make_ftrl_step(lr: float, initial_accumulator_value: float = 0.1,
+                   l1: float = 0.0, l2: float = 0.0) -> Callable:
+    from tf_yarn_amd import ops
+    state = {}
+
+    def step(shard: torch.Tensor, grad: torch.Tensor) -> None:
+        if "accum" not in state:
+            state["accum"] = torch.full_like(shard,
+                                             initial_accumulator_value)
+            state["linear"] = torch.zeros_like(shard)
+        ops.fused_ftrl(shard, grad, state["accum"], state["linear"],
+                       lr=lr, l1=l1, l2=l2)
+
+    return step
+
+
 def make_adam_step(lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8) -> Callable:
     from tf_yarn_amd import ops
