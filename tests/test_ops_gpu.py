@@ -609,9 +609,17 @@ def test_bce_head_fused_gpu():
     ref = torch.nn.functional.binary_cross_entropy_with_logits(z, labels)
     ref.backward()
     assert torch.allclose(loss, ref, atol=2e-3), (loss, ref)
+    # The gradients are of size 0.5/n: an absolute tolerance would pass an
+    # all-zero gradient.  Hold them to the float64 value within the two
+    # bf16 roundings of the kernel pair (saved sigmoid, then the result),
+    # 2**-9 each relative to the upstream 1/n = 2**-12; see
+    # test_dense_exact_gpu.py for the saturating and order-1 cases.
+    exact = (torch.sigmoid(z.detach().double()) - labels.double()) / n
     for p, p2 in zip(parts, parts2):
         assert torch.allclose(p.grad.float(), p2.grad.float(),
                               atol=1e-4), "grad mismatch"
+        assert (p.grad.double() - exact).abs().max().item() <= 2.0 ** -8 / n
+        assert p.grad.float().abs().mean().item() > 0.1 / n
 
 
 # ---- binned scatter (round-2 kernel; spec: test_binned_scatter_spec) ------

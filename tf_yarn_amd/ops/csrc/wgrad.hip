@@ -164,7 +164,7 @@ torch::Tensor wgrad_nt(torch::Tensor dy, torch::Tensor x,
   const int M = static_cast<int>(x.size(1));
   TORCH_CHECK(x.size(0) == B, "batch mismatch");
   TORCH_CHECK(N % WG_BN == 0 && M % WG_BM == 0 && B % WG_BK == 0,
-              "wgrad_nt needs N, M % 64 == 0 and B % 32 == 0");
+              "wgrad_nt needs N, M % 64 == 0 and B % 64 == 0");
   if (splitk <= 0) {
     // enough blocks for ~2 per CU
     const int tiles = (N / WG_BN) * (M / WG_BM);
