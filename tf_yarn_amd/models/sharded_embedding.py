@@ -58,6 +58,9 @@ _ALLTOALL_MODE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 # permutation).  From the round-2 A/B at the bench shape: atomic 422 us
 # flat; binned perm ~200 + applies that scale with unique/n — break-even
 # near duplication factor ~2.
+# NOTE: the atomic kernel has since dropped to ~177 us on uniform ids and
+# ~960 us on Zipf(1.2) ids (row-segment map, docs/Kernels.md), so this
+# break-even is stale and sits higher now; it has not been re-measured.
 SKEW_THRESHOLD = 2.0
 
 
@@ -257,7 +260,14 @@ class _ShardedLookup(torch.autograd.Function):
         col_offset = m._last_col_offset
         emb_grad = grad_deep_buf[:, col_offset:]
         if ctx.local_only:
-            m._deep_sink.append((flat_ids, emb_grad.contiguous()))
+            # The fused deep+wide SGD kernel reads the column slice where
+            # it lies (no 54 MB gather copy per step at the bench shape);
+            # every other consumer gets a dense [B, F*D] array.
+            if not (emb_grad.is_cuda and ops.HAVE_EXT and D % 4 == 0
+                    and emb_grad.stride(1) == 1 and not m._stateful()
+                    and emb_grad.dtype == grad_wide.dtype):
+                emb_grad = emb_grad.contiguous()
+            m._deep_sink.append((flat_ids, emb_grad))
             m._wide_sink.append((flat_ids, grad_wide.contiguous()))
             return None, None, None, None, None, None
         B = ctx.B
@@ -401,8 +411,9 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         global-mean loss split across ranks).
 
         ``stream``: optional side HIP stream.  The scatters are atomic-
-        bound (~0.8 TB/s, CUs mostly idle), so running them concurrently
-        with the dense optimizer step hides most of their latency; the
+        bound (memory-side request rate, CUs mostly idle), so running
+        them concurrently with the dense optimizer step hides most of
+        their latency; the
         CALLER must make the compute stream wait on ``stream`` before the
         next forward's gather reads the tables."""
         if stream is not None:
@@ -596,22 +607,25 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                        for i, (gw_ids, gw) in enumerate(self._wide_sink)}
         fused_wide_done = set()
         for flat_ids, grad in self._deep_sink:
+            key = flat_ids.data_ptr()
+            mate = wide_by_ids.get(key)
+            if (not use_binned
+                    and mate is not None and flat_ids.is_cuda and ops.HAVE_EXT
+                    and self.dim % 4 == 0 and wide_lr == lr
+                    and grad.dtype == mate[1].dtype
+                    and mate[0] not in fused_wide_done):
+                # grad may be the strided slice backward stashed (W == 1)
+                ops.emb_bwd_sgd_fused_wide(
+                    self.weight.data, self.wide_weight.data, flat_ids,
+                    grad, mate[1], lr=lr, scale=scale)
+                fused_wide_done.add(mate[0])
+                continue
+            # (a strided slice is gathered into a dense array here)
             grad2d = grad.reshape(flat_ids.numel(), self.dim)
             if use_binned:
                 ops.emb_bwd_sgd_binned(
                     self.weight.data, flat_ids, grad2d,
                     lr=lr, scale=scale, perm=perm_for(flat_ids))
-                continue
-            key = flat_ids.data_ptr()
-            mate = wide_by_ids.get(key)
-            if (mate is not None and flat_ids.is_cuda and ops.HAVE_EXT
-                    and self.dim % 4 == 0 and wide_lr == lr
-                    and grad2d.dtype == mate[1].dtype
-                    and mate[0] not in fused_wide_done):
-                ops.emb_bwd_sgd_fused_wide(
-                    self.weight.data, self.wide_weight.data, flat_ids,
-                    grad2d, mate[1], lr=lr, scale=scale)
-                fused_wide_done.add(mate[0])
             else:
                 ops.emb_bwd_sgd(self.weight.data, flat_ids, grad2d,
                                 lr=lr, scale=scale)

@@ -302,13 +302,20 @@ def emb_bwd_sgd_fused_wide(table: torch.Tensor, wide_table: torch.Tensor,
                            scale: float = 1.0) -> None:
     """Fused sparse update of BOTH CTR tables from one pass over the
     shared flat ids:  ``table[ids[i]] -= lr*scale*grad[i]`` and
-    ``wide_table[ids[i]] -= lr*scale*gw[i // (n//gw.numel())]``."""
+    ``wide_table[ids[i]] -= lr*scale*gw[i // (n//gw.numel())]``.
+
+    ``grad`` is ``[n, dim]``, or a ``[gw.numel(), (n//gw.numel()) * dim]``
+    column slice of a wider row-major buffer (unit column stride): the
+    kernel reads such a view in place, with no gather copy first."""
     if _on_gpu(table, ids, grad) and grad.dtype == gw.dtype:
         _require_ext()
+        if not (grad.dim() == 2 and grad.stride(1) == 1
+                and grad.shape[0] == gw.numel()
+                and grad.stride(0) >= grad.shape[1]):
+            grad = grad.contiguous()
         _C.emb_bwd_sgd_fused_wide(table, wide_table,
                                   ids.reshape(-1).contiguous(),
-                                  grad.contiguous(), gw.contiguous(),
-                                  lr, scale)
+                                  grad, gw.contiguous(), lr, scale)
         return
     n = ids.numel()
     g_div = n // gw.numel()

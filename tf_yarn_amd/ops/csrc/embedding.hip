@@ -14,9 +14,12 @@
 //  * emb_bwd_dense: grad_table[ids[i], :] += scale * g[i, :]  (for
 //                  optimizers that need the dense gradient)
 //
-// Row layout keeps consecutive d contiguous, so lanes covering one row
-// coalesce; reuse across the batch is served by L2/LLC (gather guidance:
-// guide Appendix B "Scatter/gather/embedding").
+// Row layout keeps consecutive d contiguous.  The gathers give a lane a
+// quad of a row (16 B loads; reuse across the batch is served by L2/LLC,
+// guide Appendix B "Scatter/gather/embedding").  The atomic scatters give
+// a lane ONE float, so that a wave-instruction adds whole contiguous row
+// segments: they are bound by the number of 64-byte atomic requests, not
+// by bytes (see "atomic scatter: the row-segment map" below).
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
@@ -46,85 +49,95 @@ __global__ void emb_fwd_kernel(const float* __restrict__ table,
   }
 }
 
-template <typename GIo>
-__global__ void emb_bwd_sgd_kernel(float* __restrict__ table,
-                                   const int64_t* __restrict__ ids,
-                                   const typename GIo::scalar_t* __restrict__ g,
-                                   int64_t n_rows, int64_t dim,
-                                   float neg_lr_scale) {
-  const int64_t dvec = dim >> 2;
-  const int64_t total = n_rows * dvec;
-  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       t < total; t += stride) {
-    const int64_t row = t / dvec;
-    const int64_t c4 = t - row * dvec;
-    float* dst = table + ids[row] * dim + c4 * 4;
-    float gv[4];
-    QuadIo<GIo>::load4(g, row * dvec + c4, gv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      f32_atomic_add(dst + j, neg_lr_scale * gv[j]);
-  }
-}
-
-template <typename GIo>
-__global__ void emb_bwd_dense_kernel(
-    float* __restrict__ grad_table,
-    const int64_t* __restrict__ ids,
-    const typename GIo::scalar_t* __restrict__ g,
-    int64_t n_rows, int64_t dim, float scale) {
-  const int64_t dvec = dim >> 2;
-  const int64_t total = n_rows * dvec;
-  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       t < total; t += stride) {
-    const int64_t row = t / dvec;
-    const int64_t c4 = t - row * dvec;
-    float* dst = grad_table + ids[row] * dim + c4 * 4;
-    float gv[4];
-    QuadIo<GIo>::load4(g, row * dvec + c4, gv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      f32_atomic_add(dst + j, scale * gv[j]);
-  }
-}
-
-// Fused deep+wide sparse update: the CTR models' wide (dim-1) table is
-// driven by the SAME flat ids as the deep (dim-16) table, so one kernel
-// reads the ids once and issues both updates (separate kernels re-read
-// 13.6 MB of ids and pay an extra launch; measured 84 us for the wide
-// scatter alone at b=65536).  The lane covering quad 0 of each row adds
-// the wide scalar.
-template <typename GIo>
-__global__ void emb_bwd_sgd_fused_wide_kernel(
+// ---- atomic scatter: the row-segment map ----------------------------------
+//
+// Float atomics execute at the memory side: a wave-instruction leaves L2
+// as one uncached request per 64-byte line it touches, and the chip
+// retires a fixed number of such requests per second (docs/Kernels.md,
+// "Embedding", has the model and the measurements).  So the map gives one
+// lane ONE FLOAT and `dim` consecutive lanes one update row: at dim 16 a
+// wave-instruction adds four whole 64-byte rows (4 requests), where a
+// quad-per-thread map touches 16 rows in four instructions of 16 requests
+// each - 4 requests per row instead of 1.  Rows wider than 64 floats span
+// consecutive instructions of 256 contiguous bytes; a dim that does not
+// divide 64 lets a row straddle two waves, which is correct and merely
+// costs that row one more request.
+//
+// One element per thread per grid-stride trip: at the bench shape more
+// elements per trip, a wider grid and a once-per-row id read broadcast by
+// a wave shuffle all measured within 3% of this, the atomics being the
+// only cost that shows (16 lanes reading one id are a single 8-byte
+// request).  DIM = 16 is the flagship instantiation (shifts); DIM = 0
+// reads the runtime dim, pays an int64 divide per element and serves
+// every other dim, dims that are no multiple of 4 included.  With WIDE,
+// the lane holding float 0 of a row also adds the wide (dim-1) table's
+// scalar: exactly once per update row.  With STRIDED the gradient is a
+// row-strided [batch, g_div * dim] view (a column slice of the MLP-input
+// gradient, read where backward left it): batch row b starts g_pad
+// elements later than it would in a dense array, per row before it.
+template <typename GIo, int DIM, bool WIDE, bool STRIDED>
+__device__ __forceinline__ void scatter_row_segments(
     float* __restrict__ table, float* __restrict__ wide_table,
     const int64_t* __restrict__ ids,
     const typename GIo::scalar_t* __restrict__ g,
     const typename GIo::scalar_t* __restrict__ gw,
-    int64_t n_rows, int64_t dim, int g_div,
-    float neg_lr_scale, float wide_alpha) {
-  const int64_t dvec = dim >> 2;
-  const int64_t total = n_rows * dvec;
+    int64_t n_rows, int64_t dim_rt, int g_div, int64_t g_pad,
+    float alpha, float wide_alpha) {
+  const int64_t dim = DIM ? DIM : dim_rt;
+  const int64_t total = n_rows * dim;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
        t < total; t += stride) {
-    const int64_t row = t / dvec;
-    const int64_t c4 = t - row * dvec;
+    const int64_t row = t / dim;  // a shift when DIM is a power of two
+    const int64_t c = t - row * dim;
     const int64_t id = ids[row];
-    float* dst = table + id * dim + c4 * 4;
-    float gv[4];
-    QuadIo<GIo>::load4(g, row * dvec + c4, gv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      f32_atomic_add(dst + j, neg_lr_scale * gv[j]);
-    if (c4 == 0)
+    const int64_t gi = STRIDED ? t + (row / g_div) * g_pad : t;
+    f32_atomic_add(table + id * dim + c, alpha * GIo::load(g, gi));
+    if (WIDE && c == 0)
       f32_atomic_add(wide_table + id,
                      wide_alpha * GIo::load(gw, row / g_div));
   }
 }
 
-// Scalar variants for dim % 4 != 0 (e.g. the wide part's dim-1 tables).
+template <typename GIo, int DIM>
+__global__ void emb_bwd_sgd_kernel(float* __restrict__ table,
+                                   const int64_t* __restrict__ ids,
+                                   const typename GIo::scalar_t* __restrict__ g,
+                                   int64_t n_rows, int64_t dim,
+                                   float neg_lr_scale) {
+  scatter_row_segments<GIo, DIM, false, false>(
+      table, nullptr, ids, g, nullptr, n_rows, dim, 1, 0, neg_lr_scale,
+      0.f);
+}
+
+template <typename GIo, int DIM>
+__global__ void emb_bwd_dense_kernel(
+    float* __restrict__ grad_table,
+    const int64_t* __restrict__ ids,
+    const typename GIo::scalar_t* __restrict__ g,
+    int64_t n_rows, int64_t dim, float scale) {
+  scatter_row_segments<GIo, DIM, false, false>(
+      grad_table, nullptr, ids, g, nullptr, n_rows, dim, 1, 0, scale, 0.f);
+}
+
+// Fused deep+wide sparse update: the CTR models' wide (dim-1) table is
+// driven by the SAME flat ids as the deep (dim-16) table, so one kernel
+// reads the ids once and issues both updates (separate kernels re-read
+// 13.6 MB of ids and pay an extra launch).
+template <typename GIo, int DIM, bool STRIDED>
+__global__ void emb_bwd_sgd_fused_wide_kernel(
+    float* __restrict__ table, float* __restrict__ wide_table,
+    const int64_t* __restrict__ ids,
+    const typename GIo::scalar_t* __restrict__ g,
+    const typename GIo::scalar_t* __restrict__ gw,
+    int64_t n_rows, int64_t dim, int g_div, int64_t g_pad,
+    float neg_lr_scale, float wide_alpha) {
+  scatter_row_segments<GIo, DIM, true, STRIDED>(
+      table, wide_table, ids, g, gw, n_rows, dim, g_div, g_pad,
+      neg_lr_scale, wide_alpha);
+}
+
+// Scalar gather for dim % 4 != 0 (e.g. the wide part's dim-1 tables).
 template <typename OIo>
 __global__ void emb_fwd_scalar_kernel(const float* __restrict__ table,
                                       const int64_t* __restrict__ ids,
@@ -137,21 +150,6 @@ __global__ void emb_fwd_scalar_kernel(const float* __restrict__ table,
     const int64_t row = t / dim;
     const int64_t c = t - row * dim;
     OIo::store(out, t, table[ids[row] * dim + c]);
-  }
-}
-
-template <typename GIo>
-__global__ void emb_scatter_scalar_kernel(
-    float* __restrict__ table, const int64_t* __restrict__ ids,
-    const typename GIo::scalar_t* __restrict__ g,
-    int64_t n_rows, int64_t dim, float alpha) {
-  const int64_t total = n_rows * dim;
-  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       t < total; t += stride) {
-    const int64_t row = t / dim;
-    const int64_t c = t - row * dim;
-    f32_atomic_add(table + ids[row] * dim + c, alpha * GIo::load(g, t));
   }
 }
 
@@ -280,6 +278,22 @@ void check_emb(const torch::Tensor& table, const torch::Tensor& ids,
               "ids must be contiguous int64 on GPU");
 }
 
+// Launch a row-segment scatter kernel: k16 is its dim-16 instantiation,
+// k0 the runtime-dim one.  Atomic latency is higher than load latency, so
+// the cap is 4x the streaming kernels'; the time is flat from 2048 blocks
+// to an uncapped grid (docs/Kernels.md).
+template <typename K16, typename K0, typename... Args>
+void launch_row_segments(K16 k16, K0 k0, int64_t n, int64_t dim,
+                         hipStream_t stream, Args... args) {
+  const int grid = miyarn_grid_cap(n * dim, 8192);
+  if (dim == 16)
+    hipLaunchKernelGGL(k16, dim3(grid), dim3(MIYARN_BLOCK), 0, stream,
+                       args...);
+  else
+    hipLaunchKernelGGL(k0, dim3(grid), dim3(MIYARN_BLOCK), 0, stream,
+                       args...);
+}
+
 }  // namespace
 
 torch::Tensor emb_fwd(torch::Tensor table, torch::Tensor ids,
@@ -330,36 +344,20 @@ void emb_bwd_sgd(torch::Tensor table, torch::Tensor ids, torch::Tensor grad,
   TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() &&
               grad.numel() == n * dim, "grad shape mismatch");
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const bool vec = (dim % 4 == 0);
-  // atomic RMW latency is higher than load latency: give the scheduler
-  // 4x the streaming-kernel wave count to hide it
-  int grid = miyarn_grid_cap(n * (vec ? dim / 4 : dim), 8192);
   float nls = (float)(-lr * scale);
   if (grad.scalar_type() == torch::kFloat32) {
-    if (vec)
-      hipLaunchKernelGGL(emb_bwd_sgd_kernel<F32Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         table.data_ptr<float>(), ids.data_ptr<int64_t>(),
-                         grad.data_ptr<float>(), n, dim, nls);
-    else
-      hipLaunchKernelGGL(emb_scatter_scalar_kernel<F32Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         table.data_ptr<float>(), ids.data_ptr<int64_t>(),
-                         grad.data_ptr<float>(), n, dim, nls);
+    launch_row_segments(emb_bwd_sgd_kernel<F32Io, 16>,
+                        emb_bwd_sgd_kernel<F32Io, 0>, n, dim, stream,
+                        table.data_ptr<float>(), ids.data_ptr<int64_t>(),
+                        grad.data_ptr<float>(), n, dim, nls);
   } else {
     TORCH_CHECK(grad.scalar_type() == torch::kBFloat16,
                 "grad must be fp32 or bf16");
-    auto* gptr = reinterpret_cast<unsigned short*>(grad.data_ptr());
-    if (vec)
-      hipLaunchKernelGGL(emb_bwd_sgd_kernel<Bf16Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         table.data_ptr<float>(), ids.data_ptr<int64_t>(),
-                         gptr, n, dim, nls);
-    else
-      hipLaunchKernelGGL(emb_scatter_scalar_kernel<Bf16Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         table.data_ptr<float>(), ids.data_ptr<int64_t>(),
-                         gptr, n, dim, nls);
+    launch_row_segments(emb_bwd_sgd_kernel<Bf16Io, 16>,
+                        emb_bwd_sgd_kernel<Bf16Io, 0>, n, dim, stream,
+                        table.data_ptr<float>(), ids.data_ptr<int64_t>(),
+                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
+                        n, dim, nls);
   }
 }
 
@@ -372,37 +370,21 @@ void emb_bwd_dense(torch::Tensor grad_table, torch::Tensor ids,
   TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() &&
               grad.numel() == n * dim, "grad shape mismatch");
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const bool vec = (dim % 4 == 0);
-  int grid = miyarn_grid(n * (vec ? dim / 4 : dim));
   if (grad.scalar_type() == torch::kFloat32) {
-    if (vec)
-      hipLaunchKernelGGL(emb_bwd_dense_kernel<F32Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         grad_table.data_ptr<float>(),
-                         ids.data_ptr<int64_t>(), grad.data_ptr<float>(),
-                         n, dim, (float)scale);
-    else
-      hipLaunchKernelGGL(emb_scatter_scalar_kernel<F32Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         grad_table.data_ptr<float>(),
-                         ids.data_ptr<int64_t>(), grad.data_ptr<float>(),
-                         n, dim, (float)scale);
+    launch_row_segments(emb_bwd_dense_kernel<F32Io, 16>,
+                        emb_bwd_dense_kernel<F32Io, 0>, n, dim, stream,
+                        grad_table.data_ptr<float>(),
+                        ids.data_ptr<int64_t>(), grad.data_ptr<float>(),
+                        n, dim, (float)scale);
   } else {
     TORCH_CHECK(grad.scalar_type() == torch::kBFloat16,
                 "grad must be fp32 or bf16");
-    auto* gptr = reinterpret_cast<unsigned short*>(grad.data_ptr());
-    if (vec)
-      hipLaunchKernelGGL(emb_bwd_dense_kernel<Bf16Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         grad_table.data_ptr<float>(),
-                         ids.data_ptr<int64_t>(), gptr, n, dim,
-                         (float)scale);
-    else
-      hipLaunchKernelGGL(emb_scatter_scalar_kernel<Bf16Io>, dim3(grid),
-                         dim3(MIYARN_BLOCK), 0, stream,
-                         grad_table.data_ptr<float>(),
-                         ids.data_ptr<int64_t>(), gptr, n, dim,
-                         (float)scale);
+    launch_row_segments(emb_bwd_dense_kernel<Bf16Io, 16>,
+                        emb_bwd_dense_kernel<Bf16Io, 0>, n, dim, stream,
+                        grad_table.data_ptr<float>(),
+                        ids.data_ptr<int64_t>(),
+                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
+                        n, dim, (float)scale);
   }
 }
 
@@ -529,6 +511,10 @@ void emb_bwd_sgd_sorted(torch::Tensor table, torch::Tensor sorted_ids,
   }
 }
 
+// `grad` is a dense [n, dim] array, or a 2D view [gw.numel(), g_div * dim]
+// whose rows are contiguous but lie a fixed stride apart (a column slice
+// of a wider buffer): update row b * g_div + f then reads
+// grad[b, f * dim : (f + 1) * dim] with no gather copy before the kernel.
 void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
                             torch::Tensor ids, torch::Tensor grad,
                             torch::Tensor gw, double lr, double scale) {
@@ -540,31 +526,48 @@ void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
   TORCH_CHECK(wide_table.is_cuda() && wide_table.is_contiguous() &&
               wide_table.scalar_type() == torch::kFloat32 &&
               wide_table.size(0) == table.size(0), "bad wide table");
-  TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() &&
-              grad.numel() == n * dim, "grad shape mismatch");
   TORCH_CHECK(gw.is_cuda() && gw.is_contiguous() &&
               gw.scalar_type() == grad.scalar_type() &&
-              n % gw.numel() == 0, "gw dtype/shape mismatch");
+              gw.numel() > 0 && n % gw.numel() == 0,
+              "gw dtype/shape mismatch");
   const int g_div = static_cast<int>(n / gw.numel());
+  TORCH_CHECK(grad.is_cuda() && grad.numel() == n * dim,
+              "grad shape mismatch");
+  int64_t g_pad = 0;
+  if (!grad.is_contiguous()) {
+    TORCH_CHECK(grad.dim() == 2 && grad.size(0) == gw.numel() &&
+                grad.size(1) == (int64_t)g_div * dim &&
+                grad.stride(1) == 1 && grad.stride(0) >= grad.size(1),
+                "a non-contiguous grad must be a row-strided "
+                "[gw.numel(), g_div * dim] view");
+    g_pad = grad.stride(0) - grad.size(1);
+  }
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  int grid = miyarn_grid_cap(n * (dim / 4), 8192);
   const float nls = (float)(-lr * scale);
+  auto launch = [&](auto io) {
+    using Io = decltype(io);
+    using S = typename Io::scalar_t;
+    auto* gp = reinterpret_cast<const S*>(grad.data_ptr());
+    auto* gwp = reinterpret_cast<const S*>(gw.data_ptr());
+    if (g_pad != 0)
+      launch_row_segments(emb_bwd_sgd_fused_wide_kernel<Io, 16, true>,
+                          emb_bwd_sgd_fused_wide_kernel<Io, 0, true>, n,
+                          dim, stream, table.data_ptr<float>(),
+                          wide_table.data_ptr<float>(),
+                          ids.data_ptr<int64_t>(), gp, gwp, n, dim, g_div,
+                          g_pad, nls, nls);
+    else
+      launch_row_segments(emb_bwd_sgd_fused_wide_kernel<Io, 16, false>,
+                          emb_bwd_sgd_fused_wide_kernel<Io, 0, false>, n,
+                          dim, stream, table.data_ptr<float>(),
+                          wide_table.data_ptr<float>(),
+                          ids.data_ptr<int64_t>(), gp, gwp, n, dim, g_div,
+                          g_pad, nls, nls);
+  };
   if (grad.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL(emb_bwd_sgd_fused_wide_kernel<F32Io>, dim3(grid),
-                       dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(),
-                       wide_table.data_ptr<float>(),
-                       ids.data_ptr<int64_t>(), grad.data_ptr<float>(),
-                       gw.data_ptr<float>(), n, dim, g_div, nls, nls);
+    launch(F32Io{});
   } else {
     TORCH_CHECK(grad.scalar_type() == torch::kBFloat16, "fp32/bf16 only");
-    hipLaunchKernelGGL(emb_bwd_sgd_fused_wide_kernel<Bf16Io>, dim3(grid),
-                       dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(),
-                       wide_table.data_ptr<float>(),
-                       ids.data_ptr<int64_t>(),
-                       reinterpret_cast<unsigned short*>(grad.data_ptr()),
-                       reinterpret_cast<unsigned short*>(gw.data_ptr()),
-                       n, dim, g_div, nls, nls);
+    launch(Bf16Io{});
   }
 }
