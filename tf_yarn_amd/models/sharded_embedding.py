@@ -179,11 +179,40 @@ class _ShardedLookup(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, deep_table, wide_table, module, ids, deep_out_buf,
-                col_offset):
+                col_offset, dense=None):
         m: "ShardedCriteoEmbeddings" = module
         W, B = m.world, ids.shape[0]
         D = m.dim
         device = ids.device
+        ctx.raw_ids = False
+
+        if W == 1 and dense is not None and m._fused_lookup_ok(
+                ids, dense, deep_out_buf, col_offset):
+            # One kernel from the RAW ids: offset add, deep gather, wide
+            # gather-sum and the dense / pad columns.  The fused SGD
+            # scatter adds the offsets itself too, so no flat-id array
+            # exists on this path; every other consumer of the ids (the
+            # binned scatter and its permutation, the stateful rules, a
+            # wide lr of its own) keeps the pre-added array.
+            ids = ids.contiguous()
+            wide_out = ops.emb_lookup_fused(
+                deep_table, wide_table, ids, m.full_offsets, dense,
+                deep_out_buf, col_offset)
+            if m._scatter_takes_raw_ids():
+                saved = ids
+                ctx.raw_ids = True
+            else:
+                saved = (ids + m.full_offsets.unsqueeze(0)).reshape(-1)
+                m._start_perm_async(saved)
+            ctx.module = m
+            ctx.save_for_backward(saved)
+            ctx.local_only = True
+            ctx.mark_dirty(deep_out_buf)
+            return deep_out_buf, wide_out
+
+        if dense is not None:
+            deep_out_buf[:, :dense.shape[1]] = dense
+            deep_out_buf[:, dense.shape[1]:col_offset] = 0
 
         if W == 1:
             flat = (ids + m.full_offsets.unsqueeze(0)).reshape(-1)
@@ -267,9 +296,11 @@ class _ShardedLookup(torch.autograd.Function):
                     and emb_grad.stride(1) == 1 and not m._stateful()
                     and emb_grad.dtype == grad_wide.dtype):
                 emb_grad = emb_grad.contiguous()
+            if ctx.raw_ids:  # [B, F] raw ids: the apply adds the offsets
+                m._raw_ids_keys.add(flat_ids.data_ptr())
             m._deep_sink.append((flat_ids, emb_grad))
             m._wide_sink.append((flat_ids, grad_wide.contiguous()))
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         B = ctx.B
         n_own = B * m.f_own
         # route deep grads to owners: send chunk for owner s = the
@@ -295,7 +326,7 @@ class _ShardedLookup(torch.autograd.Function):
         with commprobe.span("ag_wide"):
             dist.all_gather_into_tensor(gw_all, gw, group=m.group)
         m._wide_sink.append((flat_ids, gw_all))
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None
 
 
 class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
@@ -376,6 +407,9 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         self._deep_sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self._wide_sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self._last_col_offset = 0
+        # data_ptr of sink entries that hold RAW [B, F] ids (W == 1 fused
+        # lookup): the fused scatter adds full_offsets in the kernel
+        self._raw_ids_keys: set = set()
         self._perm_stream = None  # side stream for async pass A
         self._pending_perm = None  # (ids data_ptr, (order, starts), event)
         self._binned_auto: Optional[bool] = None  # skew probe result
@@ -388,11 +422,14 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             self.own_offsets_tiled = tiled
 
     def forward(self, ids: torch.Tensor, deep_out_buf: torch.Tensor,
-                col_offset: int
+                col_offset: int, dense: Optional[torch.Tensor] = None
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Returns (deep_buf_with_grad_fn, wide_sums [B]).  Downstream
         code MUST use the returned buffer (it carries the autograd
-        edge)."""
+        edge).  With ``dense`` (``[B, n_dense]``, ``n_dense <=
+        col_offset``, in the buffer's dtype) the columns in front of the
+        slice are written here too: ``dense``, then zeros up to
+        ``col_offset``; without it they are the caller's."""
         self._last_col_offset = col_offset
         if self.world > 1:
             self._ensure_tiled(self.world * ids.shape[0] * self.f_own,
@@ -401,8 +438,34 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             self._ensure_tiled(ids.numel(), ids.device)
         out_buf, wide = _ShardedLookup.apply(
             self.weight, self.wide_weight, self, ids, deep_out_buf,
-            col_offset)
+            col_offset, dense)
         return out_buf, wide
+
+    def _fused_lookup_ok(self, ids, dense, deep_out_buf,
+                         col_offset: int) -> bool:
+        """The W == 1 forward runs as ``ops.emb_lookup_fused``'s single
+        kernel (MIYARN_FUSED_LOOKUP=0: never)."""
+        return (ops.fused_lookup_enabled()
+                and (deep_out_buf.dtype == torch.bfloat16) == self.out_bf16
+                and ops.emb_lookup_fused_covers(
+                    self.weight, ids, dense, deep_out_buf, col_offset))
+
+    def _scatter_takes_raw_ids(self) -> bool:
+        """Whether this step's update will be the fused deep+wide SGD
+        scatter, which takes raw ``[B, F]`` ids plus ``full_offsets``:
+        both tables on SGD at one lr, and not the binned scatter.  In
+        the auto mode the one-time skew probe looks at flat ids when the
+        first update is applied; until it has decided, flat ids are
+        kept."""
+        if self._stateful() or self.wide_sparse_lr is not None \
+                or self.dim % 4 != 0:
+            return False
+        if self.dim != 16:  # the binned scatter is a dim-16 kernel
+            return True
+        mode = _binned_mode()
+        if mode != "auto":
+            return mode == "off"
+        return self._binned_auto is False
 
     @torch.no_grad()
     def apply_sparse_updates(self, lr: float, stream=None) -> None:
@@ -606,6 +669,14 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         wide_by_ids = {gw_ids.data_ptr(): (i, gw)
                        for i, (gw_ids, gw) in enumerate(self._wide_sink)}
         fused_wide_done = set()
+        raw_keys = self._raw_ids_keys
+
+        def flat_of(ids):
+            # raw [B, F] ids that did not get the fused kernel after all
+            if ids.data_ptr() in raw_keys and ids.dim() == 2:
+                return (ids + self.full_offsets.unsqueeze(0)).reshape(-1)
+            return ids
+
         for flat_ids, grad in self._deep_sink:
             key = flat_ids.data_ptr()
             mate = wide_by_ids.get(key)
@@ -617,9 +688,11 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                 # grad may be the strided slice backward stashed (W == 1)
                 ops.emb_bwd_sgd_fused_wide(
                     self.weight.data, self.wide_weight.data, flat_ids,
-                    grad, mate[1], lr=lr, scale=scale)
+                    grad, mate[1], lr=lr, scale=scale,
+                    offsets=self.full_offsets if key in raw_keys else None)
                 fused_wide_done.add(mate[0])
                 continue
+            flat_ids = flat_of(flat_ids)
             # (a strided slice is gathered into a dense array here)
             grad2d = grad.reshape(flat_ids.numel(), self.dim)
             if use_binned:
@@ -633,6 +706,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         for i, (flat_ids, gw) in enumerate(self._wide_sink):
             if i in fused_wide_done:
                 continue
+            flat_ids = flat_of(flat_ids)
             # gw layout [W, B] (or [B] local); ids layout [peer][b][j]
             if use_binned:
                 ops.emb_scatter_sum_binned(
@@ -644,7 +718,9 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             ops.emb_scatter_sum(self.wide_weight.data, ids2d, gw,
                                 alpha=-wide_lr * scale)
         self._wide_sink.clear()
+        raw_keys.clear()
 
     def clear_pending(self) -> None:
         self._deep_sink.clear()
         self._wide_sink.clear()
+        self._raw_ids_keys.clear()

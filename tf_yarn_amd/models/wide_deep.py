@@ -592,6 +592,31 @@ class WideAndDeep(nn.Module):
             # dense compute in bf16; masters are managed by the optimizer
             self.mlp = self.mlp.to(torch.bfloat16)
 
+    def _deep_tower(self, deep_in: torch.Tensor) -> torch.Tensor:
+        """``head(mlp(deep_in))``.  On the GPU in bf16 the last hidden
+        layer and the head run as one autograd node whose backward never
+        materialises the head's ``[B, width]`` input gradient
+        (``ops.LinearBiasReLUHeadFn``; same kernels and bits otherwise).
+        MIYARN_FUSED_HEAD_BWD=0 keeps the two modules apart."""
+        n = len(self.mlp)
+        last = self.mlp[n - 1] if n else None
+        head = self.head
+        if not (isinstance(last, FusedLinearReLU) and deep_in.is_cuda
+                and ops.HAVE_EXT and deep_in.dim() == 2
+                and deep_in.dtype == torch.bfloat16
+                and last.weight.dtype == torch.bfloat16
+                and last.bias.dtype == torch.bfloat16
+                and head.weight.dtype == torch.bfloat16
+                and head.bias.dtype == torch.bfloat16
+                and last.weight.shape[0] % 4 == 0
+                and ops.fused_head_bwd_enabled()):
+            return head(self.mlp(deep_in))
+        h = deep_in
+        for i in range(n - 1):
+            h = self.mlp[i](h)
+        return ops.linear_bias_relu_head(h, last.weight, last.bias,
+                                         head.weight, head.bias)
+
     def forward(self, dense: torch.Tensor, sparse_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns logits [B], or — when ``labels`` is given — the mean
@@ -604,11 +629,11 @@ class WideAndDeep(nn.Module):
             deep_in = torch.empty(
                 b, _DeepInput.DENSE_PAD + emb.F * emb.dim,
                 dtype=self.compute_dtype, device=dense.device)
-            deep_in[:, :self.dense_dim] = dense
-            deep_in[:, self.dense_dim:_DeepInput.DENSE_PAD] = 0
+            # the lookup also writes the dense and pad columns (one
+            # kernel with the gather on a single GPU)
             deep_in, wide_sum = emb(sparse_ids, deep_in,
-                                    _DeepInput.DENSE_PAD)
-            deep_out = self.head(self.mlp(deep_in))
+                                    _DeepInput.DENSE_PAD, dense=dense)
+            deep_out = self._deep_tower(deep_in)
             wide_sum = wide_sum.to(deep_out.dtype)
             wd = self.wide_dense(dense)
             if labels is not None:
@@ -619,7 +644,7 @@ class WideAndDeep(nn.Module):
         deep_in = _DeepInput.apply(
             dense, emb.weight, flat, emb.dim,
             self.compute_dtype == torch.bfloat16, emb._sink)
-        deep_out = self.head(self.mlp(deep_in))
+        deep_out = self._deep_tower(deep_in)
         wide_emb = self.wide_embedding(sparse_ids).to(deep_out.dtype)
         wd = self.wide_dense(dense)
         if labels is not None:

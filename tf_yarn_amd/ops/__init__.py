@@ -299,14 +299,20 @@ def emb_scatter_sum_binned(table: torch.Tensor, ids: torch.Tensor,
 def emb_bwd_sgd_fused_wide(table: torch.Tensor, wide_table: torch.Tensor,
                            ids: torch.Tensor, grad: torch.Tensor,
                            gw: torch.Tensor, *, lr: float,
-                           scale: float = 1.0) -> None:
+                           scale: float = 1.0,
+                           offsets: Optional[torch.Tensor] = None) -> None:
     """Fused sparse update of BOTH CTR tables from one pass over the
     shared flat ids:  ``table[ids[i]] -= lr*scale*grad[i]`` and
     ``wide_table[ids[i]] -= lr*scale*gw[i // (n//gw.numel())]``.
 
     ``grad`` is ``[n, dim]``, or a ``[gw.numel(), (n//gw.numel()) * dim]``
     column slice of a wider row-major buffer (unit column stride): the
-    kernel reads such a view in place, with no gather copy first."""
+    kernel reads such a view in place, with no gather copy first.
+
+    With ``offsets`` (``[F]`` int64), ``ids`` is the raw ``[gw.numel(), F]``
+    array of per-feature ids and update ``(b, f)`` goes to row
+    ``ids[b, f] + offsets[f]``: the kernel adds the offset itself, so the
+    caller needs no pre-added copy of the ids."""
     if _on_gpu(table, ids, grad) and grad.dtype == gw.dtype:
         _require_ext()
         if not (grad.dim() == 2 and grad.stride(1) == 1
@@ -315,8 +321,11 @@ def emb_bwd_sgd_fused_wide(table: torch.Tensor, wide_table: torch.Tensor,
             grad = grad.contiguous()
         _C.emb_bwd_sgd_fused_wide(table, wide_table,
                                   ids.reshape(-1).contiguous(),
-                                  grad, gw.contiguous(), lr, scale)
+                                  grad, gw.contiguous(), lr, scale,
+                                  offsets)
         return
+    if offsets is not None:
+        ids = ids.reshape(gw.numel(), -1) + offsets.unsqueeze(0)
     n = ids.numel()
     g_div = n // gw.numel()
     table.index_add_(0, ids.reshape(-1),
@@ -723,6 +732,83 @@ def emb_gather_sum(table: torch.Tensor, ids: torch.Tensor,
     return out.to(torch.bfloat16) if out_bf16 else out
 
 
+def _env_switch_on(name: str) -> bool:
+    """A default-on A/B switch: only an empty value or "0" turns it off."""
+    import os
+    return os.environ.get(name, "1") not in ("", "0")
+
+
+def fused_lookup_enabled() -> bool:
+    """MIYARN_FUSED_LOOKUP=0 restores the separate forward ops (offset
+    add, ``emb_fwd_into``, ``emb_gather_sum``, two fills) and the scatter
+    from pre-added flat ids."""
+    return _env_switch_on("MIYARN_FUSED_LOOKUP")
+
+
+def emb_lookup_fused_covers(table: torch.Tensor, ids: torch.Tensor,
+                            dense: Optional[torch.Tensor],
+                            out: torch.Tensor, col_offset: int) -> bool:
+    """True when :func:`emb_lookup_fused` runs as ONE kernel for these
+    operands (GPU, ``dim``, ``col_offset`` and the row stride of ``out``
+    multiples of 4, ``n_dense <= col_offset``, the feature count within
+    the kernel's LDS array)."""
+    if not (HAVE_EXT and table.is_cuda and ids.is_cuda and out.is_cuda
+            and ids.dim() == 2 and out.dim() == 2 and out.is_contiguous()
+            and out.dtype in (torch.bfloat16, torch.float32)):
+        return False
+    n_dense = 0
+    if dense is not None:
+        if not (dense.is_cuda and dense.dim() == 2
+                and dense.dtype == out.dtype):
+            return False
+        n_dense = dense.shape[1]
+    return _C.emb_lookup_fused_ok(table.shape[1], ids.shape[1], n_dense,
+                                  col_offset, out.shape[1])
+
+
+def emb_lookup_fused(table: torch.Tensor, wide_table: torch.Tensor,
+                     ids: torch.Tensor, offsets: torch.Tensor,
+                     dense: Optional[torch.Tensor], out: torch.Tensor,
+                     col_offset: int) -> torch.Tensor:
+    """The single-GPU sparse forward from the RAW ids ``[B, F]``::
+
+        out[b, col_offset + f*dim : +dim] = table[ids[b, f] + offsets[f]]
+        out[b, :n_dense] = dense[b];  out[b, n_dense:col_offset] = 0
+        wide[b] = sum_f wide_table[ids[b, f] + offsets[f]]   (returned)
+
+    ``dense`` is ``[B, n_dense]`` in ``out``'s dtype (or None); ``wide``
+    comes back in ``out``'s dtype, summed in fp32 in the order
+    ``f = 0 .. F-1`` exactly as :func:`emb_gather_sum` does.  One HIP
+    kernel where :func:`emb_lookup_fused_covers` holds; every other case,
+    the CPU included, is the composition of the separate ops, so results
+    are the same bits either way."""
+    b, f = ids.shape
+    dim = table.shape[1]
+    if emb_lookup_fused_covers(table, ids, dense, out, col_offset):
+        return _C.emb_lookup_fused(
+            table, wide_table.reshape(-1), ids.contiguous(), offsets,
+            None if dense is None else dense.contiguous(), out, col_offset)
+    if _on_gpu(table, ids, out):
+        _require_ext()
+    n_dense = 0
+    if dense is not None:
+        n_dense = dense.shape[1]
+        out[:, :n_dense] = dense
+    if col_offset > n_dense:
+        out[:, n_dense:col_offset] = 0
+    flat = (ids + offsets.unsqueeze(0)).reshape(-1)
+    out_bf16 = out.dtype == torch.bfloat16
+    if not _on_gpu(table, ids, out) or (
+            dim % 4 == 0 and col_offset % 4 == 0
+            and out.shape[1] % 4 == 0 and out.is_contiguous()):
+        emb_fwd_into(table, flat, out, col_offset)
+    else:  # shapes emb_fwd_into does not take: gather, then place
+        rows = emb_fwd(table, flat, out_bf16)
+        out[:, col_offset:col_offset + f * dim] = \
+            rows.reshape(b, f * dim).to(out.dtype)
+    return emb_gather_sum(wide_table, flat.reshape(b, f), out_bf16)
+
+
 def emb_scatter_sum(table: torch.Tensor, ids: torch.Tensor,
                     grad: torch.Tensor, alpha: float) -> None:
     """table[ids[b, f], 0] += alpha * grad[b] (gather-sum backward)."""
@@ -979,3 +1065,85 @@ class LinearBiasReLU(torch.autograd.Function):
 def linear_bias_relu(x: torch.Tensor, weight: torch.Tensor,
                      bias: torch.Tensor) -> torch.Tensor:
     return LinearBiasReLU.apply(x, weight, bias)
+
+
+# ---- last hidden layer + single-logit head ---------------------------------
+
+def fused_head_bwd_enabled() -> bool:
+    """MIYARN_FUSED_HEAD_BWD=0 restores the separate last layer and head
+    (the head's backward materialises its ``[B, width]`` input gradient)."""
+    return _env_switch_on("MIYARN_FUSED_HEAD_BWD")
+
+
+def head_relu_bwd_db(dl: torch.Tensor, w_head: torch.Tensor,
+                     y: torch.Tensor):
+    """Backward of "ReLU, then single-logit head" with respect to the
+    ReLU's input: ``(dz, dbias)`` of
+    ``bias_relu_bwd_db(dl[:, None] * w_head[None, :], y)`` — to the bit —
+    without the ``[B, width]`` outer product in memory.  ``dl [B]`` is the
+    logit gradient, ``w_head [width]`` the head's weight, ``y [B, width]``
+    the ReLU's output.  bf16 widths the oct kernel takes run as one kernel;
+    everything else forms the product and takes the two-step path."""
+    if _on_gpu(dl, w_head, y) and HAVE_EXT and dl.dtype == y.dtype \
+            and w_head.dtype == y.dtype and y.dim() == 2 \
+            and y.size(1) % 4 == 0 and y.size(1) <= 8192:
+        dz, dbias = _C.head_relu_bwd_db(
+            dl.contiguous(), w_head.contiguous(), y.contiguous(),
+            y.dtype == torch.bfloat16)
+        return dz, dbias.to(y.dtype)
+    if _on_gpu(dl, w_head, y):
+        _require_ext()
+    dz = bias_relu_bwd(dl.unsqueeze(1) * w_head.unsqueeze(0), y)
+    return dz, dz.sum(dim=0)
+
+
+class LinearBiasReLUHeadFn(torch.autograd.Function):
+    """``relu(x @ w.T + bias) . w_head + b_head``: the last hidden layer
+    and the single-logit head as ONE autograd node, so that backward goes
+    from the logit gradient straight to the layer's ``dz``
+    (:func:`head_relu_bwd_db`) instead of writing and re-reading the head's
+    ``[B, width]`` input gradient.  Forward is :class:`LinearBiasReLU`'s
+    followed by :class:`ScalarHeadFn`'s, backward computes what the two
+    nodes computed, kernel for kernel, except for that product."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, w_head, b_head):
+        if _custom_fwd_ok(x, weight, bias):
+            y = _C.gemm_bt(x, weight, bias, True)
+        elif _lt_fwd_ok(x, weight, bias):
+            y = _C.lt_linear(x, weight, bias.contiguous(), True)
+        else:
+            y = bias_relu_fwd(x.matmul(weight.t()), bias)
+        ctx.save_for_backward(x, weight, y, w_head)
+        if _on_gpu(y, w_head) and y.size(1) % 4 == 0 \
+                and y.size(1) <= 512 and b_head.numel() == 1:
+            _require_ext()
+            return _C.row_dot(y.contiguous(), w_head.contiguous(),
+                              b_head.reshape(1))
+        return y @ w_head + b_head
+
+    @staticmethod
+    def backward(ctx, dl):
+        x, weight, y, w_head = ctx.saved_tensors
+        dl = dl.contiguous()
+        dw_head = db_head = None
+        if ctx.needs_input_grad[3]:
+            dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
+        if ctx.needs_input_grad[4]:
+            db_head = dl.sum().reshape(1).to(w_head.dtype)
+        dz, dbias = head_relu_bwd_db(dl, w_head, y)
+        dx = dz.matmul(weight)
+        kernel = _custom_wgrad_kernel(dz, x)
+        if kernel is not None:
+            dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16)
+            if dw.dtype != weight.dtype:
+                dw = dw.to(weight.dtype)
+        else:
+            dw = dz.t().matmul(x)
+        return dx, dw, dbias, dw_head, db_head
+
+
+def linear_bias_relu_head(x: torch.Tensor, weight: torch.Tensor,
+                          bias: torch.Tensor, w_head: torch.Tensor,
+                          b_head: torch.Tensor) -> torch.Tensor:
+    return LinearBiasReLUHeadFn.apply(x, weight, bias, w_head, b_head)

@@ -41,9 +41,17 @@ void emb_bwd_sgd_sorted(torch::Tensor table, torch::Tensor sorted_ids,
                         torch::Tensor grad, double lr, double scale);
 void emb_bwd_dense(torch::Tensor grad_table, torch::Tensor ids,
                    torch::Tensor grad, double scale);
-void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
-                            torch::Tensor ids, torch::Tensor grad,
-                            torch::Tensor gw, double lr, double scale);
+void emb_bwd_sgd_fused_wide_offs(torch::Tensor table,
+                                 torch::Tensor wide_table, torch::Tensor ids,
+                                 torch::Tensor grad, torch::Tensor gw,
+                                 double lr, double scale,
+                                 c10::optional<torch::Tensor> offsets);
+bool emb_lookup_fused_ok(int64_t dim, int64_t n_features, int64_t n_dense,
+                         int64_t col_offset, int64_t out_cols);
+torch::Tensor emb_lookup_fused(torch::Tensor table, torch::Tensor wide_table,
+                               torch::Tensor ids, torch::Tensor offsets,
+                               c10::optional<torch::Tensor> dense,
+                               torch::Tensor out, int64_t col_offset);
 
 torch::Tensor emb_gather_sum(torch::Tensor table, torch::Tensor ids,
                              int64_t batch, bool out_bf16);
@@ -135,6 +143,10 @@ torch::Tensor bias_relu_bwd(torch::Tensor dy, torch::Tensor y);
 std::vector<torch::Tensor> bias_relu_bwd_db(torch::Tensor dy,
                                             torch::Tensor y,
                                             bool dbias_bf16);
+std::vector<torch::Tensor> head_relu_bwd_db(torch::Tensor dl,
+                                            torch::Tensor w_head,
+                                            torch::Tensor y,
+                                            bool dbias_bf16);
 torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
 
 // lt_linear.hip
@@ -176,8 +188,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused sparse embedding grad scatter + SGD update");
   m.def("emb_bwd_sgd_sorted", &emb_bwd_sgd_sorted,
         "Atomic-free segmented scatter+SGD over SORTED ids");
-  m.def("emb_bwd_sgd_fused_wide", &emb_bwd_sgd_fused_wide,
-        "Fused deep scatter+SGD + wide scalar scatter (shared ids)");
+  m.def("emb_bwd_sgd_fused_wide", &emb_bwd_sgd_fused_wide_offs,
+        "Fused deep scatter+SGD + wide scalar scatter (shared ids; with "
+        "offsets, raw [batch, features] ids)",
+        py::arg("table"), py::arg("wide_table"), py::arg("ids"),
+        py::arg("grad"), py::arg("gw"), py::arg("lr"), py::arg("scale"),
+        py::arg("offsets") = py::none());
+  m.def("emb_lookup_fused_ok", &emb_lookup_fused_ok,
+        "Whether emb_lookup_fused covers (dim, features, n_dense, "
+        "col_offset, out_cols)");
+  m.def("emb_lookup_fused", &emb_lookup_fused,
+        "Offset add + deep gather into a slice + wide gather-sum + dense/"
+        "pad columns in one kernel (returns the wide sums)",
+        py::arg("table"), py::arg("wide_table"), py::arg("ids"),
+        py::arg("offsets"), py::arg("dense"), py::arg("out"),
+        py::arg("col_offset"));
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
   m.def("sparse_adagrad_apply", &sparse_adagrad_apply,
@@ -241,6 +266,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_relu_bwd_db", &bias_relu_bwd_db,
         "Fused ReLU backward + dbias reduction (returns [dx, dbias])",
         py::arg("dy"), py::arg("y"), py::arg("dbias_bf16") = false);
+  m.def("head_relu_bwd_db", &head_relu_bwd_db,
+        "ReLU backward + dbias of the layer under a single-logit head, from "
+        "dl and w_head (no outer product; returns [dz, dbias])",
+        py::arg("dl"), py::arg("w_head"), py::arg("y"),
+        py::arg("dbias_bf16") = false);
   m.def("emb_fwd_into", &emb_fwd_into,
         "Embedding gather into a slice of a larger 2D buffer");
   m.def("emb_gather_sum", &emb_gather_sum,

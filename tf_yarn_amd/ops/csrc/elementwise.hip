@@ -157,8 +157,24 @@ __global__ void bias_relu_bwd_dbpart_kernel(
 // 256-wide MLP tail ran at 1.9 TB/s with a 1D map) still fill the chip.
 // Requires octs to divide blockDim; one partial row per (block, slot).
 // dx keeps the original dy bits where the mask passes (no round trip).
-__global__ void bias_relu_bwd_dbpart8_kernel(
-    const unsigned short* __restrict__ dy,
+//
+// HEAD: the layer feeds a single-logit head, so its dy is the outer
+// product dl[b] * w_head[m] and is never materialised: the thread keeps
+// its oct of w_head in registers, reads one dl per row and forms
+// g = bf16(float(dl) * float(w)) - one round-to-nearest-even of an exact
+// fp32 product, the bits torch's bf16 multiply stores.  Everything after
+// the load (mask, partial sums, their order) is shared, so dx and the
+// partial slab match the two-step path bit for bit.
+__device__ __forceinline__ unsigned short bf16_mul_rne(float a, float b) {
+  const float p = a * b;
+  return p != p ? (unsigned short)0x7fc0 : f32_to_bf16(p);  // torch's NaN
+}
+
+template <bool HEAD>
+__device__ __forceinline__ void bias_relu_bwd_dbpart8_body(
+    const unsigned short* __restrict__ dy,      // !HEAD
+    const unsigned short* __restrict__ dl,      // HEAD: [rows]
+    const unsigned short* __restrict__ w_head,  // HEAD: [cols]
     const unsigned short* __restrict__ y,
     unsigned short* __restrict__ dx,
     float* __restrict__ dbias_part,  // [gridDim.x * rpb][cols]
@@ -170,16 +186,27 @@ __global__ void bias_relu_bwd_dbpart8_kernel(
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  float wf[8];
+  if (HEAD) {
+    const bf16x8 wv = reinterpret_cast<const bf16x8*>(w_head)[q];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wf[j] = bf16_to_f32(wv[j]);
+  }
   const int64_t slot = (int64_t)blockIdx.x * rpb + rid;
   const int64_t row_stride = (int64_t)gridDim.x * rpb * DB_ROWS;
   for (int64_t r0 = slot * DB_ROWS; r0 < rows; r0 += row_stride) {
     const int nr = min((int64_t)DB_ROWS, rows - r0);
     bf16x8 gv[DB_ROWS], yv[DB_ROWS];
+    float df[DB_ROWS];  // HEAD: dl of the row; the product is formed at use
 #pragma unroll
     for (int rr = 0; rr < DB_ROWS; ++rr)
-      if (rr < nr)
-        gv[rr] = reinterpret_cast<const bf16x8*>(
-            dy)[(r0 + rr) * octs + q];
+      if (rr < nr) {
+        if (HEAD)
+          df[rr] = bf16_to_f32(dl[r0 + rr]);
+        else
+          gv[rr] = reinterpret_cast<const bf16x8*>(
+              dy)[(r0 + rr) * octs + q];
+      }
 #pragma unroll
     for (int rr = 0; rr < DB_ROWS; ++rr)
       if (rr < nr)
@@ -192,8 +219,10 @@ __global__ void bias_relu_bwd_dbpart8_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const bool keep = bf16_to_f32(yv[rr][j]) > 0.f;
-          out[j] = keep ? gv[rr][j] : (unsigned short)0;
-          if (keep) acc[j] += bf16_to_f32(gv[rr][j]);
+          const unsigned short g =
+              HEAD ? bf16_mul_rne(df[rr], wf[j]) : gv[rr][j];
+          out[j] = keep ? g : (unsigned short)0;
+          if (keep) acc[j] += bf16_to_f32(g);
         }
         reinterpret_cast<bf16x8*>(dx)[(r0 + rr) * octs + q] = out;
       }
@@ -204,6 +233,25 @@ __global__ void bias_relu_bwd_dbpart8_kernel(
   for (int j = 0; j < 4; ++j) { lo[j] = acc[j]; hi[j] = acc[4 + j]; }
   reinterpret_cast<f32x4*>(part)[q * 2] = lo;
   reinterpret_cast<f32x4*>(part)[q * 2 + 1] = hi;
+}
+
+__global__ void bias_relu_bwd_dbpart8_kernel(
+    const unsigned short* __restrict__ dy,
+    const unsigned short* __restrict__ y,
+    unsigned short* __restrict__ dx,
+    float* __restrict__ dbias_part, int64_t rows, int64_t cols) {
+  bias_relu_bwd_dbpart8_body<false>(dy, nullptr, nullptr, y, dx, dbias_part,
+                                    rows, cols);
+}
+
+__global__ void head_relu_bwd_dbpart8_kernel(
+    const unsigned short* __restrict__ dl,
+    const unsigned short* __restrict__ w_head,
+    const unsigned short* __restrict__ y,
+    unsigned short* __restrict__ dx,
+    float* __restrict__ dbias_part, int64_t rows, int64_t cols) {
+  bias_relu_bwd_dbpart8_body<true>(nullptr, dl, w_head, y, dx, dbias_part,
+                                   rows, cols);
 }
 
 // dx = dy * (y > 0)
@@ -390,6 +438,42 @@ torch::Tensor bias_relu_bwd(torch::Tensor dy, torch::Tensor y) {
 
 torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
 
+namespace {
+
+// Launch shape of the oct kernel.  bias_relu_bwd_db and head_relu_bwd_db
+// both take it from here: the row-to-partial map, and so every bit of
+// dbias, depends on block, rpb and grid.
+struct DbOctPlan {
+  bool ok;      // the oct kernel covers this dtype and width
+  int block8;   // threads per block
+  int64_t rpb;  // row slots per block
+  int grid;
+};
+
+DbOctPlan db_oct_plan(bool bf16, int64_t rows, int64_t cols) {
+  const int64_t octs = cols / 8;
+  DbOctPlan p;
+  p.ok = bf16 && cols % 8 == 0 && octs >= 1 && octs <= MIYARN_BLOCK &&
+         MIYARN_BLOCK % octs == 0;
+  // Wide layers measured best with one row slot per block (block = octs);
+  // narrow ones need multiple slots to fill the chip (65536x256 ran at
+  // 1.9 TB/s single-slot vs 2.2 multi-slot).
+  p.block8 = octs >= 128 ? static_cast<int>(octs) : MIYARN_BLOCK;
+  p.rpb = p.ok ? p.block8 / octs : 1;
+  // Fill the chip: narrow layers (256 cols -> rpb=8) were capped at
+  // 256 blocks (1/CU) by a MAX_BLOCKS/rpb partial-row bound and ran
+  // at 1.9 TB/s.  Allow up to 4x MAX_BLOCKS partial rows (>= 4
+  // blocks/CU for every width) — unbounded partials measured the
+  // dbias reduce growing +18 us/step, eating half the streaming win.
+  p.grid = static_cast<int>(std::min<int64_t>(
+      (rows + p.rpb * DB_ROWS - 1) / (p.rpb * DB_ROWS),
+      std::min<int64_t>(MIYARN_MAX_BLOCKS,
+                        4 * MIYARN_MAX_BLOCKS / p.rpb)));
+  return p;
+}
+
+}  // namespace
+
 std::vector<torch::Tensor> bias_relu_bwd_db(torch::Tensor dy,
                                             torch::Tensor y,
                                             bool dbias_bf16) {
@@ -410,25 +494,12 @@ std::vector<torch::Tensor> bias_relu_bwd_db(torch::Tensor dy,
       std::min<int64_t>(MIYARN_BLOCK, ((quads + 63) / 64) * 64));
   int grid = static_cast<int>(std::min<int64_t>(
       (rows + DB_ROWS - 1) / DB_ROWS, MIYARN_MAX_BLOCKS));
-  const int64_t octs = cols / 8;
-  const bool oct_ok = dy.scalar_type() == torch::kBFloat16 &&
-                      cols % 8 == 0 && octs <= MIYARN_BLOCK &&
-                      MIYARN_BLOCK % octs == 0;
-  // Wide layers measured best with one row slot per block (block = octs);
-  // narrow ones need multiple slots to fill the chip (65536x256 ran at
-  // 1.9 TB/s single-slot vs 2.2 multi-slot).
-  const int block8 = octs >= 128 ? static_cast<int>(octs) : MIYARN_BLOCK;
-  const int64_t rpb = oct_ok ? block8 / octs : 1;
-  if (oct_ok)
-    // Fill the chip: narrow layers (256 cols -> rpb=8) were capped at
-    // 256 blocks (1/CU) by a MAX_BLOCKS/rpb partial-row bound and ran
-    // at 1.9 TB/s.  Allow up to 4x MAX_BLOCKS partial rows (>= 4
-    // blocks/CU for every width) — unbounded partials measured the
-    // dbias reduce growing +18 us/step, eating half the streaming win.
-    grid = static_cast<int>(std::min<int64_t>(
-        (rows + rpb * DB_ROWS - 1) / (rpb * DB_ROWS),
-        std::min<int64_t>(MIYARN_MAX_BLOCKS,
-                          4 * MIYARN_MAX_BLOCKS / rpb)));
+  const DbOctPlan plan = db_oct_plan(
+      dy.scalar_type() == torch::kBFloat16, rows, cols);
+  const bool oct_ok = plan.ok;
+  const int block8 = plan.block8;
+  const int64_t rpb = plan.rpb;
+  if (oct_ok) grid = plan.grid;
   // Atomic-free column partials: one row per block (per slot for the
   // oct kernel), reduced below.
   auto part = torch::empty({grid * rpb, cols},
@@ -463,6 +534,43 @@ std::vector<torch::Tensor> bias_relu_bwd_db(torch::Tensor dy,
     if (dbias_bf16) dbias = dbias.to(torch::kBFloat16);
   }
   return {dx, dbias};
+}
+
+// bias_relu_bwd_db(dl[:, None] * w_head[None, :], y) without the
+// [rows, cols] outer product in memory: same launch shape, partial slab
+// and reduce, so dz and dbias are that call's to the bit.  Widths the oct
+// kernel does not take form the product and go through that call.
+std::vector<torch::Tensor> head_relu_bwd_db(torch::Tensor dl,
+                                            torch::Tensor w_head,
+                                            torch::Tensor y,
+                                            bool dbias_bf16) {
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && y.dim() == 2,
+              "y must be a contiguous 2D GPU tensor");
+  const int64_t rows = y.size(0);
+  const int64_t cols = y.size(1);
+  TORCH_CHECK(dl.is_cuda() && dl.is_contiguous() && dl.numel() == rows &&
+              dl.scalar_type() == y.scalar_type(), "dl must be [rows]");
+  TORCH_CHECK(w_head.is_cuda() && w_head.is_contiguous() &&
+              w_head.numel() == cols &&
+              w_head.scalar_type() == y.scalar_type(),
+              "w_head must be [cols]");
+  const DbOctPlan plan = db_oct_plan(
+      y.scalar_type() == torch::kBFloat16, rows, cols);
+  if (!plan.ok || rows == 0)
+    return bias_relu_bwd_db(
+        dl.reshape({rows, 1}) * w_head.reshape({1, cols}), y, dbias_bf16);
+  auto dz = torch::empty_like(y);
+  auto part = torch::empty({plan.grid * plan.rpb, cols},
+                           y.options().dtype(torch::kFloat32));
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL(head_relu_bwd_dbpart8_kernel, dim3(plan.grid),
+                     dim3(plan.block8), 0, stream,
+                     reinterpret_cast<unsigned short*>(dl.data_ptr()),
+                     reinterpret_cast<unsigned short*>(w_head.data_ptr()),
+                     reinterpret_cast<unsigned short*>(y.data_ptr()),
+                     reinterpret_cast<unsigned short*>(dz.data_ptr()),
+                     part.data_ptr<float>(), rows, cols);
+  return {dz, reduce_splitk(part, dbias_bf16)};
 }
 
 void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale) {

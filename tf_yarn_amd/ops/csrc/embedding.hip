@@ -4,7 +4,8 @@
 // embedding gradient reduce).  All categorical tables are concatenated into
 // one [total_rows, D] fp32 buffer; Python pre-adds per-feature row offsets
 // into the flat id tensor, so the kernels are pure row gather / row
-// scatter:
+// scatter (the single-GPU step's emb_lookup_fused and the fused SGD
+// scatter take the raw ids and add the offsets themselves):
 //
 //  * emb_fwd:      out[i, :] = table[ids[i], :]          (out fp32 or bf16;
 //                  bf16 out fuses the mixed-precision cast into the gather)
@@ -75,14 +76,18 @@ __global__ void emb_fwd_kernel(const float* __restrict__ table,
 // row-strided [batch, g_div * dim] view (a column slice of the MLP-input
 // gradient, read where backward left it): batch row b starts g_pad
 // elements later than it would in a dense array, per row before it.
-template <typename GIo, int DIM, bool WIDE, bool STRIDED>
+// With OFFS, `ids` is the raw [batch, g_div] array of per-feature ids and
+// the kernel adds offsets[row % g_div] itself, so no pre-added copy of the
+// ids has to exist; the other instantiations never look at `offsets`.
+template <typename GIo, int DIM, bool WIDE, bool STRIDED, bool OFFS = false>
 __device__ __forceinline__ void scatter_row_segments(
     float* __restrict__ table, float* __restrict__ wide_table,
     const int64_t* __restrict__ ids,
     const typename GIo::scalar_t* __restrict__ g,
     const typename GIo::scalar_t* __restrict__ gw,
     int64_t n_rows, int64_t dim_rt, int g_div, int64_t g_pad,
-    float alpha, float wide_alpha) {
+    float alpha, float wide_alpha,
+    const int64_t* __restrict__ offsets = nullptr) {
   const int64_t dim = DIM ? DIM : dim_rt;
   const int64_t total = n_rows * dim;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
@@ -90,7 +95,8 @@ __device__ __forceinline__ void scatter_row_segments(
        t < total; t += stride) {
     const int64_t row = t / dim;  // a shift when DIM is a power of two
     const int64_t c = t - row * dim;
-    const int64_t id = ids[row];
+    int64_t id = ids[row];
+    if (OFFS) id += offsets[row - (row / g_div) * g_div];
     const int64_t gi = STRIDED ? t + (row / g_div) * g_pad : t;
     f32_atomic_add(table + id * dim + c, alpha * GIo::load(g, gi));
     if (WIDE && c == 0)
@@ -135,6 +141,22 @@ __global__ void emb_bwd_sgd_fused_wide_kernel(
   scatter_row_segments<GIo, DIM, true, STRIDED>(
       table, wide_table, ids, g, gw, n_rows, dim, g_div, g_pad,
       neg_lr_scale, wide_alpha);
+}
+
+// The same update from the raw [batch, g_div] ids: offsets[f] is added in
+// the kernel, so the single-GPU step never writes (forward) nor re-reads
+// (here) a 13.6 MB pre-added copy of the ids.
+template <typename GIo, int DIM, bool STRIDED>
+__global__ void emb_bwd_sgd_fused_wide_offs_kernel(
+    float* __restrict__ table, float* __restrict__ wide_table,
+    const int64_t* __restrict__ ids, const int64_t* __restrict__ offsets,
+    const typename GIo::scalar_t* __restrict__ g,
+    const typename GIo::scalar_t* __restrict__ gw,
+    int64_t n_rows, int64_t dim, int g_div, int64_t g_pad,
+    float neg_lr_scale, float wide_alpha) {
+  scatter_row_segments<GIo, DIM, true, STRIDED, true>(
+      table, wide_table, ids, g, gw, n_rows, dim, g_div, g_pad,
+      neg_lr_scale, wide_alpha, offsets);
 }
 
 // Scalar gather for dim % 4 != 0 (e.g. the wide part's dim-1 tables).
@@ -211,6 +233,79 @@ __global__ void emb_fwd_into_kernel(const float* __restrict__ table,
     for (int j = 0; j < 4; ++j) vv[j] = v[j];
     QuadIo<OIo>::store4(out, b * out_stride_q + off_q + f * dvec + c4,
                         vv);
+  }
+}
+
+// The whole single-GPU sparse forward in one pass over the raw ids: the
+// per-feature offset add, the deep gather into the MLP-input slice
+// (emb_fwd_into_kernel's cast and layout), the wide gather-sum, and the
+// dense / zero-pad columns in front of the slice.  Separately these were
+// a torch int64 add that wrote a 13.6 MB flat-id array, two kernels that
+// each read it back, and two small torch fills.
+//
+// A block owns chunks of `rows_per_chunk` whole batch rows and walks a
+// chunk's output quads in row-major order, so a row of `out` is written
+// front to back by consecutive lanes.  The lane that holds quad 0 of
+// (b, f) also loads the wide scalar of that id and parks it in LDS; after
+// the barrier ONE thread per batch row adds its F scalars in the order
+// f = 0 .. F-1 from 0.f, which is emb_gather_sum_kernel's sum to the bit
+// (a tree or shuffle reduction would not be).
+#define LOOKUP_ROWS 32          // batch rows of a chunk
+#define LOOKUP_LDS_FLOATS 2048  // parked wide scalars: rows_per_chunk * F
+
+template <typename OIo>
+__global__ void emb_lookup_fused_kernel(
+    const float* __restrict__ table, const float* __restrict__ wide_table,
+    const int64_t* __restrict__ ids, const int64_t* __restrict__ offsets,
+    const typename OIo::scalar_t* __restrict__ dense,
+    typename OIo::scalar_t* __restrict__ out,
+    typename OIo::scalar_t* __restrict__ wide_out,
+    int64_t batch, int dim, int F, int rows_per_chunk,
+    int64_t out_stride_q, int off_q, int n_dense) {
+  __shared__ float wide_s[LOOKUP_LDS_FLOATS];
+  const int dvec = dim >> 2;
+  const int ipr = off_q + F * dvec;  // quads written per batch row
+  const int64_t n_chunks = (batch + rows_per_chunk - 1) / rows_per_chunk;
+  for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    const int64_t b0 = chunk * rows_per_chunk;
+    const int nr = (int)min((int64_t)rows_per_chunk, batch - b0);
+    const int items = nr * ipr;
+    for (int t = threadIdx.x; t < items; t += blockDim.x) {
+      const int r = t / ipr;
+      const int i = t - r * ipr;
+      const int64_t b = b0 + r;
+      float vv[4];
+      if (i < off_q) {
+        // dense features, then zeros up to the slice (bf16 -> f32 -> bf16
+        // returns the stored bits)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = i * 4 + j;
+          vv[j] = col < n_dense
+                      ? OIo::load(dense, b * (int64_t)n_dense + col)
+                      : 0.f;
+        }
+      } else {
+        const int gq = i - off_q;
+        const int f = gq / dvec;
+        const int c4 = gq - f * dvec;
+        const int64_t id = ids[b * F + f] + offsets[f];
+        f32x4 v = reinterpret_cast<const f32x4*>(table + id * dim)[c4];
+        if (c4 == 0) wide_s[r * F + f] = wide_table[id];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) vv[j] = v[j];
+      }
+      QuadIo<OIo>::store4(out, b * out_stride_q + i, vv);
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < nr; r += blockDim.x) {
+      float acc = 0.f;
+      const float* row = wide_s + r * F;
+#pragma unroll 4
+      for (int f = 0; f < F; ++f) acc += row[f];
+      OIo::store(wide_out, b0 + r, acc);
+    }
+    __syncthreads();  // the next chunk overwrites wide_s
   }
 }
 
@@ -480,6 +575,85 @@ void emb_fwd_into(torch::Tensor table, torch::Tensor ids,
   }
 }
 
+// True when emb_lookup_fused_kernel covers the shape; the Python wrapper
+// asks before it chooses between the kernel and the separate ops.
+bool emb_lookup_fused_ok(int64_t dim, int64_t n_features, int64_t n_dense,
+                         int64_t col_offset, int64_t out_cols) {
+  return dim > 0 && dim % 4 == 0 && col_offset >= 0 &&
+         col_offset % 4 == 0 && out_cols % 4 == 0 && n_dense >= 0 &&
+         n_dense <= col_offset && n_features >= 1 &&
+         n_features <= LOOKUP_LDS_FLOATS &&
+         col_offset + n_features * dim <= out_cols &&
+         // a chunk's quads are counted in an int
+         LOOKUP_ROWS * (col_offset / 4 + n_features * (dim / 4)) <
+             (int64_t(1) << 30);
+}
+
+// out[b, col_offset + f*dim + c] = table[ids[b, f] + offsets[f], c];
+// out[b, :n_dense] = dense[b]; out[b, n_dense:col_offset] = 0; returns
+// wide[b] = sum_f wide_table[ids[b, f] + offsets[f]] in out's dtype.
+torch::Tensor emb_lookup_fused(torch::Tensor table, torch::Tensor wide_table,
+                               torch::Tensor ids, torch::Tensor offsets,
+                               c10::optional<torch::Tensor> dense,
+                               torch::Tensor out, int64_t col_offset) {
+  const int64_t dim = table.size(1);
+  check_emb(table, ids, dim);
+  TORCH_CHECK(ids.dim() == 2, "ids must be the raw [batch, features] array");
+  const int64_t batch = ids.size(0);
+  const int64_t F = ids.size(1);
+  TORCH_CHECK(offsets.is_cuda() && offsets.is_contiguous() &&
+              offsets.scalar_type() == torch::kInt64 &&
+              offsets.numel() == F, "offsets must be int64 [features]");
+  TORCH_CHECK(wide_table.is_cuda() && wide_table.is_contiguous() &&
+              wide_table.scalar_type() == torch::kFloat32 &&
+              wide_table.numel() == table.size(0), "bad wide table");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 2 &&
+              out.size(0) == batch,
+              "out must be a contiguous [batch, cols] GPU tensor");
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 ||
+              out.scalar_type() == torch::kFloat32, "fp32/bf16 only");
+  int64_t n_dense = 0;
+  const void* dense_ptr = nullptr;
+  if (dense.has_value()) {
+    TORCH_CHECK(dense->is_cuda() && dense->is_contiguous() &&
+                dense->dim() == 2 && dense->size(0) == batch &&
+                dense->scalar_type() == out.scalar_type(),
+                "dense must be contiguous [batch, n_dense] of out's dtype");
+    n_dense = dense->size(1);
+    dense_ptr = dense->data_ptr();
+  }
+  TORCH_CHECK(emb_lookup_fused_ok(dim, F, n_dense, col_offset, out.size(1)),
+              "shape not covered by emb_lookup_fused (dim, col_offset and "
+              "out stride % 4, n_dense <= col_offset, features <= ",
+              LOOKUP_LDS_FLOATS, ")");
+  if (bounds_debug_enabled())
+    debug_check_ids(ids + offsets.unsqueeze(0), table.size(0));
+  auto wide = torch::empty({batch}, out.options());
+  if (batch == 0) return wide;
+  const int rpc = static_cast<int>(
+      std::min<int64_t>(LOOKUP_ROWS, LOOKUP_LDS_FLOATS / F));
+  const int grid = static_cast<int>(std::min<int64_t>(
+      (batch + rpc - 1) / rpc, MIYARN_MAX_BLOCKS));
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  auto launch = [&](auto io) {
+    using Io = decltype(io);
+    using S = typename Io::scalar_t;
+    hipLaunchKernelGGL(emb_lookup_fused_kernel<Io>, dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       table.data_ptr<float>(), wide_table.data_ptr<float>(),
+                       ids.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       static_cast<const S*>(dense_ptr),
+                       reinterpret_cast<S*>(out.data_ptr()),
+                       reinterpret_cast<S*>(wide.data_ptr()), batch,
+                       (int)dim, (int)F, rpc, out.size(1) / 4,
+                       (int)(col_offset / 4), (int)n_dense);
+  };
+  if (out.scalar_type() == torch::kBFloat16)
+    launch(Bf16Io{});
+  else
+    launch(F32Io{});
+  return wide;
+}
 
 void emb_bwd_sgd_sorted(torch::Tensor table, torch::Tensor sorted_ids,
                         torch::Tensor grad, double lr, double scale) {
@@ -515,13 +689,29 @@ void emb_bwd_sgd_sorted(torch::Tensor table, torch::Tensor sorted_ids,
 // whose rows are contiguous but lie a fixed stride apart (a column slice
 // of a wider buffer): update row b * g_div + f then reads
 // grad[b, f * dim : (f + 1) * dim] with no gather copy before the kernel.
-void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
-                            torch::Tensor ids, torch::Tensor grad,
-                            torch::Tensor gw, double lr, double scale) {
+// With `offsets` [g_div], `ids` holds the raw per-feature ids, row-major
+// [gw.numel(), g_div], and update row b * g_div + f goes to table row
+// ids[b, f] + offsets[f].
+void emb_bwd_sgd_fused_wide_offs(torch::Tensor table,
+                                 torch::Tensor wide_table, torch::Tensor ids,
+                                 torch::Tensor grad, torch::Tensor gw,
+                                 double lr, double scale,
+                                 c10::optional<torch::Tensor> offsets) {
   const int64_t dim = table.size(1);
   const int64_t n = ids.numel();
   check_emb(table, ids, dim);
-  debug_check_ids(ids, table.size(0));
+  if (offsets.has_value()) {
+    TORCH_CHECK(offsets->is_cuda() && offsets->is_contiguous() &&
+                offsets->scalar_type() == torch::kInt64 &&
+                gw.numel() > 0 &&
+                offsets->numel() * gw.numel() == n,
+                "offsets must be int64 [ids.numel() / gw.numel()]");
+    if (bounds_debug_enabled())
+      debug_check_ids(ids.reshape({gw.numel(), offsets->numel()}) +
+                          offsets->unsqueeze(0), table.size(0));
+  } else {
+    debug_check_ids(ids, table.size(0));
+  }
   TORCH_CHECK(dim % 4 == 0, "fused wide update needs dim % 4 == 0");
   TORCH_CHECK(wide_table.is_cuda() && wide_table.is_contiguous() &&
               wide_table.scalar_type() == torch::kFloat32 &&
@@ -549,6 +739,24 @@ void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
     using S = typename Io::scalar_t;
     auto* gp = reinterpret_cast<const S*>(grad.data_ptr());
     auto* gwp = reinterpret_cast<const S*>(gw.data_ptr());
+    if (offsets.has_value()) {
+      const int64_t* op = offsets->data_ptr<int64_t>();
+      if (g_pad != 0)
+        launch_row_segments(
+            emb_bwd_sgd_fused_wide_offs_kernel<Io, 16, true>,
+            emb_bwd_sgd_fused_wide_offs_kernel<Io, 0, true>, n, dim, stream,
+            table.data_ptr<float>(), wide_table.data_ptr<float>(),
+            ids.data_ptr<int64_t>(), op, gp, gwp, n, dim, g_div, g_pad, nls,
+            nls);
+      else
+        launch_row_segments(
+            emb_bwd_sgd_fused_wide_offs_kernel<Io, 16, false>,
+            emb_bwd_sgd_fused_wide_offs_kernel<Io, 0, false>, n, dim, stream,
+            table.data_ptr<float>(), wide_table.data_ptr<float>(),
+            ids.data_ptr<int64_t>(), op, gp, gwp, n, dim, g_div, g_pad, nls,
+            nls);
+      return;
+    }
     if (g_pad != 0)
       launch_row_segments(emb_bwd_sgd_fused_wide_kernel<Io, 16, true>,
                           emb_bwd_sgd_fused_wide_kernel<Io, 0, true>, n,
@@ -570,4 +778,11 @@ void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
     TORCH_CHECK(grad.scalar_type() == torch::kBFloat16, "fp32/bf16 only");
     launch(Bf16Io{});
   }
+}
+
+void emb_bwd_sgd_fused_wide(torch::Tensor table, torch::Tensor wide_table,
+                            torch::Tensor ids, torch::Tensor grad,
+                            torch::Tensor gw, double lr, double scale) {
+  emb_bwd_sgd_fused_wide_offs(table, wide_table, ids, grad, gw, lr, scale,
+                              c10::nullopt);
 }
