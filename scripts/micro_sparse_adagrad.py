@@ -2,8 +2,12 @@
 """Micro-benchmark of the stateful sparse apply (Adagrad, FTRL) at the
 bench shape (b=65536, 26 features x 1M rows, dim 16 deep + dim 1 wide,
 bf16 grads).  --rule picks the update rule: adagrad (both tables), ftrl
-(both tables) or adagrad+ftrl (deep Adagrad, wide FTRL: the
-wide-and-deep recipe).
+(both tables), adagrad+ftrl (deep Adagrad, wide FTRL: the wide-and-deep
+recipe), rowwise+adagrad / rowwise+ftrl (row-wise Adagrad on the deep
+table, one state value per row, with that wide rule) or rowwise (the deep
+table alone, no wide companion).  The three row-wise settings also time
+pass 2 of their element-wise counterpart on the same tables in the same
+process, before and after a second row-wise window.
 
 Timed, on identical inputs:
   * the fused deep+wide update: pass 1 (atomic accumulate, the existing
@@ -69,6 +73,13 @@ def _baseline_rows(rule, table, states, uniq, g):
     """One table of the torch baseline: gather the unique rows, apply the
     rule elementwise, copy back.  The FTRL rule is the one `ops` uses."""
     w = table.index_select(0, uniq)
+    if rule == "rowwise":
+        ss = (g * g).sum(dim=1)
+        s = states[0].index_select(0, uniq) + ss / torch.full_like(ss, DIM)
+        states[0].index_copy_(0, uniq, s)
+        table.index_copy_(0, uniq, w.addcdiv_(
+            g, s.sqrt_().add_(EPS).unsqueeze(1), value=-LR))
+        return
     if rule == "adagrad":
         s = states[0].index_select(0, uniq).addcmul_(g, g)
         states[0].index_copy_(0, uniq, s)
@@ -87,6 +98,8 @@ def torch_baseline(rules, table, states, wide, wide_states, ids, grad, gw):
     g = torch.zeros(uniq.numel(), DIM, device=ids.device)
     g.index_add_(0, inv, grad.float())
     _baseline_rows(rules[0], table, states, uniq, g)
+    if len(rules) == 1:
+        return
     g_div = ids.numel() // gw.numel()
     gwide = torch.zeros(uniq.numel(), device=ids.device)
     gwide.index_add_(0, inv, gw.float().repeat_interleave(g_div))
@@ -95,6 +108,8 @@ def torch_baseline(rules, table, states, wide, wide_states, ids, grad, gw):
 
 
 def make_states(rule, table):
+    if rule == "rowwise":
+        return [torch.zeros(table.shape[0], device=table.device)]
     if rule == "adagrad":
         return [torch.zeros_like(table)]
     return [torch.full_like(table, 0.1), torch.zeros_like(table)]
@@ -107,14 +122,18 @@ def main():
     ap.add_argument("--zipf", type=float, default=0.0,
                     help="Zipf exponent (> 1) for the ids; 0 = uniform")
     ap.add_argument("--rule", default="adagrad",
-                    choices=["adagrad", "ftrl", "adagrad+ftrl"],
+                    choices=["adagrad", "ftrl", "adagrad+ftrl", "rowwise",
+                             "rowwise+adagrad", "rowwise+ftrl"],
                     help="update rule of the deep[+wide] table")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
-    rules = tuple(args.rule.split("+")) * (1 if "+" in args.rule else 2)
+    rules = tuple(args.rule.split("+"))
+    if len(rules) == 1 and args.rule != "rowwise":
+        rules *= 2
+    pair = len(rules) == 2
     tag = args.rule.replace("+", "_")
 
     torch.manual_seed(0)
@@ -126,7 +145,7 @@ def main():
     table = torch.randn(n_rows, DIM, device="cuda")
     wide = torch.randn(n_rows, 1, device="cuda")
     states = make_states(rules[0], table)
-    wide_states = make_states(rules[1], wide)
+    wide_states = make_states(rules[1], wide) if pair else []
     ws = ops.SparseWorkspace(table, wide)
     uniq = int(torch.unique(ids).numel())
     C = ops._C
@@ -162,6 +181,35 @@ def main():
             ops.emb_bwd_ftrl_fused_wide(
                 table, *states, wide, *wide_states, ids, grad, gw, lr=LR,
                 l1=L1, l2=L2, workspace=ws)
+    elif args.rule == "rowwise":
+        def pass2():
+            C.sparse_rowwise_adagrad_apply(
+                table, states[0], ws.acc, ws.stamp, ids, ws.next_epoch(),
+                LR, EPS)
+
+        def total():
+            ops.emb_bwd_rowwise_adagrad(table, states[0], ids, grad, lr=LR,
+                                        eps=EPS, workspace=ws)
+    elif args.rule == "rowwise+adagrad":
+        def pass2():
+            C.sparse_rowwise_adagrad_apply_fused_wide(
+                table, states[0], ws.acc, wide, wide_states[0],
+                ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
+
+        def total():
+            ops.emb_bwd_rowwise_adagrad_fused_wide(
+                table, states[0], wide, wide_states[0], ids, grad, gw,
+                lr=LR, eps=EPS, workspace=ws)
+    elif args.rule == "rowwise+ftrl":
+        def pass2():
+            C.sparse_rowwise_adagrad_ftrl_apply_fused_wide(
+                table, states[0], ws.acc, wide, *wide_states, ws.wide_acc,
+                ws.stamp, ids, ws.next_epoch(), LR, EPS, LR, L1, L2)
+
+        def total():
+            ops.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+                table, states[0], wide, *wide_states, ids, grad, gw,
+                lr=LR, eps=EPS, l1=L1, l2=L2, workspace=ws)
     else:
         def pass2():
             C.sparse_adagrad_ftrl_apply_fused_wide(
@@ -174,6 +222,9 @@ def main():
                 lr=LR, eps=EPS, l1=L1, l2=L2, workspace=ws)
 
     def single(rule, tbl, sts, g, workspace, wide_table):
+        if rule == "rowwise":
+            return lambda: ops.emb_bwd_rowwise_adagrad(
+                tbl, sts[0], ids, g, lr=LR, eps=EPS, workspace=workspace)
         if rule == "adagrad":
             fn = ops.emb_bwd_adagrad_wide if wide_table \
                 else ops.emb_bwd_adagrad
@@ -185,17 +236,54 @@ def main():
 
     record("sgd_fused_wide", lambda: C.emb_bwd_sgd_fused_wide(
         table, wide, ids, grad, gw, LR, 1.0))
-    record(f"{tag}_pass1_accumulate", lambda: C.emb_bwd_sgd_fused_wide(
-        ws.acc, ws.wide_acc, ids, grad, gw, -1.0, 1.0))
+    if pair:
+        record(f"{tag}_pass1_accumulate", lambda: C.emb_bwd_sgd_fused_wide(
+            ws.acc, ws.wide_acc, ids, grad, gw, -1.0, 1.0))
+    else:  # the deep table alone accumulates through emb_bwd_dense
+        record(f"{tag}_pass1_accumulate",
+               lambda: C.emb_bwd_dense(ws.acc, ids, grad, 1.0))
     # consumes the accumulated sums once, then runs on a clean
     # accumulator: same claims and row traffic every call
     record(f"{tag}_pass2_claim_apply", pass2)
     assert not ws.acc.any() and not ws.wide_acc.any()
-    record(f"{tag}_fused_wide_total", total)
-    record(f"{tag}_deep_only",
-           single(rules[0], table, states, grad, ws, False))
-    record(f"{tag}_wide_only",
-           single(rules[1], wide, wide_states, gw, ws.wide_view(), True))
+    if pair:
+        record(f"{tag}_fused_wide_total", total)
+        record(f"{tag}_deep_only",
+               single(rules[0], table, states, grad, ws, False))
+        record(f"{tag}_wide_only", single(rules[1], wide, wide_states, gw,
+                                          ws.wide_view(), True))
+        if rules[0] == "rowwise":
+            # the element-wise pair with the same wide rule on the same
+            # tables, same process: figures of two processes differ by more
+            # than the rules do
+            elem = torch.zeros_like(table)
+            if rules[1] == "adagrad":
+                def elem_pass2():
+                    C.sparse_adagrad_apply_fused_wide(
+                        table, elem, ws.acc, wide, wide_states[0],
+                        ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
+            else:
+                def elem_pass2():
+                    C.sparse_adagrad_ftrl_apply_fused_wide(
+                        table, elem, ws.acc, wide, *wide_states,
+                        ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR,
+                        EPS, LR, L1, L2)
+            record("elementwise_pair_pass2_claim_apply", elem_pass2)
+            record(f"{tag}_pass2_claim_apply_again", pass2)
+            record("elementwise_pair_pass2_claim_apply_again", elem_pass2)
+            del elem
+    else:
+        record(f"{tag}_total", total)
+        # element-wise Adagrad on the same deep table, same process
+        elem = torch.zeros_like(table)
+        record("adagrad_deep_pass2_claim_apply",
+               lambda: C.sparse_adagrad_apply(
+                   table, elem, ws.acc, ws.stamp, ids, ws.next_epoch(), LR,
+                   EPS))
+        record("adagrad_deep_total",
+               single("adagrad", table, [elem], grad, ws, False))
+        record(f"{tag}_pass2_claim_apply_again", pass2)
+        del elem
     record("torch_unique_index_add", lambda: torch_baseline(
         rules, table, states, wide, wide_states, ids, grad, gw))
 

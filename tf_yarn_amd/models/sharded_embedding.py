@@ -36,7 +36,8 @@ import torch.distributed as dist
 from torch import nn
 
 from tf_yarn_amd import ops
-from tf_yarn_amd.models.wide_deep import SparseOptimizerMixin
+from tf_yarn_amd.models.wide_deep import (SparseOptimizerMixin,
+                                          _default_wide_rule)
 from tf_yarn_amd.utils import commprobe
 
 logger = logging.getLogger(__name__)
@@ -340,6 +341,9 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
     ``state_sum`` / ``wide_state_sum``, ``"ftrl"`` keeps ``ftrl_accum`` +
     ``ftrl_linear`` / ``wide_ftrl_accum`` + ``wide_ftrl_linear`` (per rank
     like the tables; a table owns state for its own rule only).
+    ``sparse_optimizer="rowwise_adagrad"`` keeps ``state_sum_row``, one
+    value per owned deep row, and defaults the wide table to
+    ``"adagrad"``; it is not a rule for the dim-1 wide table.
     ``sparse_l1`` / ``sparse_l2`` regularise FTRL, ``wide_sparse_lr``
     fixes the wide table's lr.  The binned scatter and its forward-time
     permutation prefetch are SGD-only and run only when both tables are
@@ -378,7 +382,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         self.wide_weight._miyarn_sparse = True
         self.wide_weight._miyarn_sharded = True
         if wide_sparse_optimizer is None:
-            wide_sparse_optimizer = sparse_optimizer
+            wide_sparse_optimizer = _default_wide_rule(sparse_optimizer)
         self.sparse_optimizer = sparse_optimizer
         self.wide_sparse_optimizer = wide_sparse_optimizer
         self._init_sparse_optimizer(
@@ -546,7 +550,8 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
 
     # rule pairs (deep, wide) that have a fused deep+wide entry point
     _FUSED_PAIRS = (("adagrad", "adagrad"), ("adagrad", "ftrl"),
-                    ("ftrl", "ftrl"))
+                    ("ftrl", "ftrl"), ("rowwise_adagrad", "adagrad"),
+                    ("rowwise_adagrad", "ftrl"))
 
     def _apply_fused_pair(self, flat_ids, grad2d, gw, lr: float,
                           wide_lr: float, scale: float, ws) -> None:
@@ -569,7 +574,18 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                 self.wide_ftrl_accum, self.wide_ftrl_linear, flat_ids,
                 grad2d, gw, lr=lr, wide_lr=wide_lr, l1=self.sparse_l1,
                 l2=self.sparse_l2, scale=scale, workspace=ws)
-        else:  # Adagrad pair at two rates: the fused kernel has one lr
+        elif pair == ("rowwise_adagrad", "adagrad") and wide_lr == lr:
+            ops.emb_bwd_rowwise_adagrad_fused_wide(
+                deep, self.state_sum_row, wide, self.wide_state_sum,
+                flat_ids, grad2d, gw, lr=lr, eps=self.sparse_eps,
+                scale=scale, workspace=ws)
+        elif pair == ("rowwise_adagrad", "ftrl"):
+            ops.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+                deep, self.state_sum_row, wide, self.wide_ftrl_accum,
+                self.wide_ftrl_linear, flat_ids, grad2d, gw, lr=lr,
+                eps=self.sparse_eps, wide_lr=wide_lr, l1=self.sparse_l1,
+                l2=self.sparse_l2, scale=scale, workspace=ws)
+        else:  # an Adagrad pair at two rates: the fused kernels have one lr
             self._sparse_apply_one(self.sparse_optimizer, "", deep,
                                    flat_ids, grad2d, lr, scale, ws,
                                    wide=False)

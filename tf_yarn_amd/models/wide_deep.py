@@ -40,14 +40,31 @@ CRITEO_SPARSE = 26
 DEFAULT_TABLE_SIZES = [1_000_000] * CRITEO_SPARSE
 
 
+# the rules every table accepts, the dim-1 wide table included
 SPARSE_OPTIMIZERS = ("sgd", "adagrad", "ftrl")
+# tables with dim > 1 also take the rule with one state value per row
+DEEP_SPARSE_OPTIMIZERS = SPARSE_OPTIMIZERS + ("rowwise_adagrad",)
 
 
-def _check_sparse_rule(name: str, value: str) -> str:
-    if value not in SPARSE_OPTIMIZERS:
+def _check_sparse_rule(name: str, value: str, dim: int = 1) -> str:
+    """``dim``: the row width of the table the rule is for."""
+    if value == "rowwise_adagrad" and dim <= 1:
         raise ValueError(
-            f"{name} must be one of {SPARSE_OPTIMIZERS}, got {value!r}")
+            f"{name}={value!r}: a dim-1 table's row-wise rule is "
+            f"\"adagrad\" (one state value per row already); pick one of "
+            f"{SPARSE_OPTIMIZERS}")
+    allowed = DEEP_SPARSE_OPTIMIZERS if dim > 1 else SPARSE_OPTIMIZERS
+    if value not in allowed:
+        raise ValueError(
+            f"{name} must be one of {allowed}, got {value!r}")
     return value
+
+
+def _default_wide_rule(sparse_optimizer: str) -> str:
+    """The wide table's rule when none is given: the deep table's, and
+    "adagrad" under a row-wise deep table (the same rule at dim 1)."""
+    return ("adagrad" if sparse_optimizer == "rowwise_adagrad"
+            else sparse_optimizer)
 
 
 class SparseOptimizerMixin:
@@ -66,6 +83,10 @@ class SparseOptimizerMixin:
       (checkpoints carry them).  ``state_sum`` and ``ftrl_accum`` start at
       ``sparse_initial_accumulator``, ``ftrl_linear`` at 0.  A table owns
       state for its own rule only;
+    * ``"rowwise_adagrad"`` (tables with ``dim > 1`` only): ``state_sum_row``,
+      ONE persistent fp32 value per row (shape ``[rows]``, filled with
+      ``sparse_initial_accumulator``) and no ``state_sum``: ``rows`` floats
+      of state instead of ``rows x dim``;
     * a non-persistent accumulator + int32 row stamp, allocated on the
       first apply (:class:`tf_yarn_amd.ops.SparseWorkspace`, shared by
       the pair whatever their rules).
@@ -83,8 +104,9 @@ class SparseOptimizerMixin:
                                ) -> None:
         """``tables``: state-name prefix -> (table parameter, rule), deep
         table first; the first stateful entry owns the row stamp."""
-        for prefix, (_, rule) in tables.items():
-            _check_sparse_rule(f"{prefix}sparse_optimizer", rule)
+        for prefix, (table, rule) in tables.items():
+            _check_sparse_rule(f"{prefix}sparse_optimizer", rule,
+                               table.shape[1])
         if not (sparse_l1 >= 0 and sparse_l2 >= 0):
             raise ValueError("sparse_l1 and sparse_l2 must be >= 0, got "
                              f"{sparse_l1!r}, {sparse_l2!r}")
@@ -103,14 +125,19 @@ class SparseOptimizerMixin:
         for prefix, (table, rule) in tables.items():
             if rule == "sgd":
                 continue
+            like = table.detach()
             if rule == "adagrad":
                 fills = {prefix + "state_sum": init}
+            elif rule == "rowwise_adagrad":
+                fills = {prefix + "state_sum_row": init}
+                like = like[:, 0]  # one state value per row: [rows]
             else:
                 fills = {prefix + "ftrl_accum": init,
                          prefix + "ftrl_linear": 0.0}
             for name, value in fills.items():
                 self.register_buffer(
-                    name, torch.full_like(table.detach(), value),
+                    name, torch.full(like.shape, value, dtype=like.dtype,
+                                     device=like.device),
                     persistent=True)
             acc = ("_adagrad_acc" if n_stateful == 0
                    else f"_adagrad_acc{n_stateful}")
@@ -129,6 +156,12 @@ class SparseOptimizerMixin:
                           workspace, wide: bool) -> None:
         """One single-table stateful update (``rule`` is not "sgd") with
         this module's state buffers ``<prefix>...``."""
+        if rule == "rowwise_adagrad":  # never the wide table's rule
+            ops.emb_bwd_rowwise_adagrad(
+                table, getattr(self, prefix + "state_sum_row"), ids, grad,
+                lr=lr, eps=self.sparse_eps, scale=scale,
+                workspace=workspace)
+            return
         if rule == "adagrad":
             fn = ops.emb_bwd_adagrad_wide if wide else ops.emb_bwd_adagrad
             fn(table, getattr(self, prefix + "state_sum"), ids, grad,
@@ -215,7 +248,9 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
     ``sparse_optimizer="adagrad"`` replaces the scatter+SGD update with
     sparse Adagrad (state in the ``state_sum`` buffer), ``"ftrl"`` with
     sparse FTRL-proximal (``ftrl_accum`` / ``ftrl_linear``, regularised
-    by ``sparse_l1`` / ``sparse_l2``).
+    by ``sparse_l1`` / ``sparse_l2``), ``"rowwise_adagrad"`` (``dim > 1``)
+    with row-wise sparse Adagrad, whose whole state is one fp32 value per
+    row (``state_sum_row``).
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
@@ -237,7 +272,7 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         self.weight = nn.Parameter(weight)
         self.weight._miyarn_sparse = True  # dense reducer must skip it
         self.sparse_optimizer = _check_sparse_rule("sparse_optimizer",
-                                                   sparse_optimizer)
+                                                   sparse_optimizer, dim)
         self._init_sparse_optimizer(
             sparse_eps, sparse_initial_accumulator,
             {"": (self.weight, sparse_optimizer)},
@@ -531,13 +566,21 @@ class WideAndDeep(nn.Module):
                  wide_sparse_optimizer: Optional[str] = None,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
                  wide_sparse_lr: Optional[float] = None):
-        """``sparse_optimizer`` ("sgd", "adagrad" or "ftrl") picks the
-        update rule of the embedding tables; it is NOT inferred from the
-        dense optimizer, whose lr is what ``apply_sparse_updates(lr)``
-        receives.  ``wide_sparse_optimizer`` picks the wide table's rule
-        (None: the same as ``sparse_optimizer``), so the textbook
-        wide-and-deep recipe is ``sparse_optimizer="adagrad",
-        wide_sparse_optimizer="ftrl", sparse_l1=...``.
+        """``sparse_optimizer`` ("sgd", "adagrad", "ftrl" or
+        "rowwise_adagrad") picks the update rule of the embedding tables;
+        it is NOT inferred from the dense optimizer, whose lr is what
+        ``apply_sparse_updates(lr)`` receives.  ``wide_sparse_optimizer``
+        picks the wide table's rule (None: the same as
+        ``sparse_optimizer``), so the textbook wide-and-deep recipe is
+        ``sparse_optimizer="adagrad", wide_sparse_optimizer="ftrl",
+        sparse_l1=...``.
+
+        ``"rowwise_adagrad"`` keeps one state value per deep ROW
+        (``state_sum_row``, ``rows`` floats instead of ``rows x dim``).
+        It is a rule for the deep table only: the wide table is dim 1,
+        where the same rule is ``"adagrad"``, which is also its default
+        under a row-wise deep table; ``wide_sparse_optimizer=
+        "rowwise_adagrad"`` raises ``ValueError``.
 
         ``sparse_l1`` / ``sparse_l2``: FTRL's regularisation strengths
         (L1 > 0 is what makes untrained-away weights exactly 0).
@@ -548,7 +591,7 @@ class WideAndDeep(nn.Module):
         super().__init__()
         table_sizes = table_sizes or DEFAULT_TABLE_SIZES
         if wide_sparse_optimizer is None:
-            wide_sparse_optimizer = sparse_optimizer
+            wide_sparse_optimizer = _default_wide_rule(sparse_optimizer)
         sparse_kw = dict(
             sparse_optimizer=sparse_optimizer, sparse_eps=sparse_eps,
             sparse_initial_accumulator=sparse_initial_accumulator,

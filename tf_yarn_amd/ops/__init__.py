@@ -678,6 +678,130 @@ def emb_bwd_ftrl_fused_wide(
                       workspace=ws.wide_view() if ws is not None else None)
 
 
+# ---- row-wise sparse Adagrad -----------------------------------------------
+
+def _rowwise_adagrad_rows_ref(table: torch.Tensor, state_row: torch.Tensor,
+                              flat_ids: torch.Tensor, rows: torch.Tensor,
+                              lr: float, eps: float, scale: float) -> None:
+    """Reference: coalesce duplicate ids, then one row-wise Adagrad step
+    on the unique rows.  The mean of squares is a true division by ``dim``
+    (tensor / tensor, never a multiply by a reciprocal)."""
+    uniq, inv = torch.unique(flat_ids, return_inverse=True)
+    dim = rows.shape[1]
+    g = torch.zeros(uniq.numel(), dim, dtype=torch.float32,
+                    device=rows.device)
+    g.index_add_(0, inv, rows.float())
+    g.mul_(scale)
+    ss = (g * g).sum(dim=1)
+    s = state_row.index_select(0, uniq) + ss / torch.full_like(ss, dim)
+    state_row.index_copy_(0, uniq, s)
+    w = table.index_select(0, uniq).addcdiv_(
+        g, s.sqrt().add_(eps).unsqueeze(1), value=-lr)
+    table.index_copy_(0, uniq, w)
+
+
+def emb_bwd_rowwise_adagrad(table: torch.Tensor, state_row: torch.Tensor,
+                            ids: torch.Tensor, grad: torch.Tensor, *,
+                            lr: float, eps: float = 1e-10,
+                            scale: float = 1.0,
+                            workspace: Optional[SparseWorkspace] = None
+                            ) -> None:
+    """Row-wise sparse Adagrad on the rows named by ``ids``: ONE fp32
+    accumulator value per row (``state_row``, contiguous ``[rows]``), the
+    running mean of the row's squared gradient, in place of
+    :func:`emb_bwd_adagrad`'s table-shaped ``state_sum``.  For each
+    unique id u, in fp32::
+
+        G[u, :]       = scale * sum(grad[i] for ids[i] == u)
+        state_row[u] += (sum_c G[u, c]^2) / dim
+        table[u, :]  -= lr * G[u, :] / (sqrt(state_row[u]) + eps)
+
+    with the NEW ``state_row[u]`` in the last line.  Rows not in ``ids``
+    are neither read nor written.  ``grad`` fp32 or bf16, table and state
+    fp32, any ``dim >= 1`` (``dim == 1`` is element-wise Adagrad).
+
+    GPU: pass 1 of :func:`emb_bwd_adagrad` into ``workspace.acc``, then
+    the row-wise claim kernels of ``csrc/sparse_adagrad.hip``."""
+    flat = ids.reshape(-1)
+    if _on_gpu(table, state_row, ids, grad):
+        _require_ext()
+        ws = workspace if workspace is not None else SparseWorkspace(table)
+        _C.emb_bwd_rowwise_adagrad(table, state_row, ws.acc, ws.stamp,
+                                   flat.contiguous(), grad.contiguous(),
+                                   ws.next_epoch(), lr, eps, scale)
+        return
+    _rowwise_adagrad_rows_ref(table, state_row, flat,
+                              grad.reshape(flat.numel(), -1), lr, eps,
+                              scale)
+
+
+def emb_bwd_rowwise_adagrad_fused_wide(
+        table: torch.Tensor, state_row: torch.Tensor,
+        wide_table: torch.Tensor, wide_state_sum: torch.Tensor,
+        ids: torch.Tensor, grad: torch.Tensor, gw: torch.Tensor, *,
+        lr: float, eps: float = 1e-10, scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """Row-wise sparse Adagrad on the deep table and sparse Adagrad on the
+    wide scalars from the shared flat ids, at one ``lr`` and ``eps``: the
+    winner of a deep row also applies the wide scalar.  ``workspace`` must
+    have been built with ``wide_table``.  Shapes the fused kernel does not
+    cover (:func:`_fused_pair_covers`) take the two single-table ops on
+    the shared stamp, as in :func:`emb_bwd_adagrad_fused_wide`."""
+    ws = None
+    if _on_gpu(table, ids, grad, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseWorkspace(table, wide_table)
+        if _fused_pair_covers(table, grad, gw):
+            _C.emb_bwd_rowwise_adagrad_fused_wide(
+                table, state_row, ws.acc, wide_table, wide_state_sum,
+                ws.wide_acc, ws.stamp, ids.reshape(-1).contiguous(),
+                grad.contiguous(), gw.reshape(-1).contiguous(),
+                ws.next_epoch(), lr, eps, scale)
+            return
+    emb_bwd_rowwise_adagrad(table, state_row, ids, grad, lr=lr, eps=eps,
+                            scale=scale, workspace=ws)
+    emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
+                         eps=eps, scale=scale,
+                         workspace=ws.wide_view() if ws is not None
+                         else None)
+
+
+def emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+        table: torch.Tensor, state_row: torch.Tensor,
+        wide_table: torch.Tensor, wide_accum: torch.Tensor,
+        wide_linear: torch.Tensor, ids: torch.Tensor, grad: torch.Tensor,
+        gw: torch.Tensor, *, lr: float, eps: float = 1e-10,
+        wide_lr: Optional[float] = None, l1: float = 0.0, l2: float = 0.0,
+        scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """The wide-and-deep recipe with a row-wise deep table: row-wise
+    sparse Adagrad (``lr``, ``eps``) on the deep table and sparse FTRL
+    (``wide_lr``, default ``lr``; ``l1``, ``l2``) on the wide scalars, one
+    claim per row for both.  Fallback rule as in
+    :func:`emb_bwd_rowwise_adagrad_fused_wide`."""
+    wide_lr = lr if wide_lr is None else wide_lr
+    _check_ftrl_args(wide_lr, l1, l2)
+    ws = None
+    if _on_gpu(table, ids, grad, gw):
+        _require_ext()
+        ws = workspace if workspace is not None \
+            else SparseWorkspace(table, wide_table)
+        if _fused_pair_covers(table, grad, gw):
+            _C.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+                table, state_row, ws.acc, wide_table, wide_accum,
+                wide_linear, ws.wide_acc, ws.stamp,
+                ids.reshape(-1).contiguous(), grad.contiguous(),
+                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, eps,
+                wide_lr, l1, l2, scale)
+            return
+    emb_bwd_rowwise_adagrad(table, state_row, ids, grad, lr=lr, eps=eps,
+                            scale=scale, workspace=ws)
+    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
+                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
+                      workspace=ws.wide_view() if ws is not None else None)
+
+
 # ---- elementwise -----------------------------------------------------------
 
 def bias_relu_fwd(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:

@@ -124,6 +124,40 @@ void emb_bwd_ftrl_fused_wide(
     torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
     torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
     double lr, double wide_lr, double l1, double l2, double scale);
+void sparse_rowwise_adagrad_apply(torch::Tensor table,
+                                  torch::Tensor state_row,
+                                  torch::Tensor acc, torch::Tensor stamp,
+                                  torch::Tensor ids, int64_t epoch,
+                                  double lr, double eps);
+void sparse_rowwise_adagrad_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    int64_t epoch, double lr, double eps);
+void sparse_rowwise_adagrad_ftrl_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, int64_t epoch, double lr, double eps,
+    double wide_lr, double l1, double l2);
+void emb_bwd_rowwise_adagrad(torch::Tensor table, torch::Tensor state_row,
+                             torch::Tensor acc, torch::Tensor stamp,
+                             torch::Tensor ids, torch::Tensor grad,
+                             int64_t epoch, double lr, double eps,
+                             double scale);
+void emb_bwd_rowwise_adagrad_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
+    double eps, double scale);
+void emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
+    double lr, double eps, double wide_lr, double l1, double l2,
+    double scale);
 
 // binned_scatter.hip
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
@@ -233,6 +267,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Deep sparse Adagrad + wide sparse FTRL (shared ids)");
   m.def("emb_bwd_ftrl_fused_wide", &emb_bwd_ftrl_fused_wide,
         "Sparse FTRL for the deep + wide pair (shared ids)");
+  m.def("sparse_rowwise_adagrad_apply", &sparse_rowwise_adagrad_apply,
+        "Row-wise sparse Adagrad pass 2: claim each touched row once, "
+        "reduce its squares, update state_row[rows] + table");
+  m.def("sparse_rowwise_adagrad_apply_fused_wide",
+        &sparse_rowwise_adagrad_apply_fused_wide,
+        "Pass 2 for a deep row-wise Adagrad + wide Adagrad pair");
+  m.def("sparse_rowwise_adagrad_ftrl_apply_fused_wide",
+        &sparse_rowwise_adagrad_ftrl_apply_fused_wide,
+        "Pass 2 for a deep row-wise Adagrad + wide FTRL pair");
+  m.def("emb_bwd_rowwise_adagrad", &emb_bwd_rowwise_adagrad,
+        "Row-wise sparse Adagrad (one state value per row): atomic "
+        "accumulate + once-per-row claim/apply");
+  m.def("emb_bwd_rowwise_adagrad_fused_wide",
+        &emb_bwd_rowwise_adagrad_fused_wide,
+        "Deep row-wise sparse Adagrad + wide sparse Adagrad (shared ids)");
+  m.def("emb_bwd_rowwise_adagrad_ftrl_fused_wide",
+        &emb_bwd_rowwise_adagrad_ftrl_fused_wide,
+        "Deep row-wise sparse Adagrad + wide sparse FTRL (shared ids)");
   m.def("fused_ftrl", &fused_ftrl, "Fused dense FTRL-proximal step");
   m.def("bias_relu_fwd", &bias_relu_fwd, "Fused bias+ReLU forward");
   m.def("bias_relu_bwd", &bias_relu_bwd, "Fused ReLU backward");

@@ -1,5 +1,5 @@
-// Stateful sparse optimizers for the embedding tables (Adagrad, FTRL):
-// accumulate, then claim.
+// Stateful sparse optimizers for the embedding tables (Adagrad, FTRL,
+// row-wise Adagrad): accumulate, then claim.
 //
 // A stateful sparse optimizer must sum a batch's duplicate ids BEFORE it
 // touches the state, then update state and weight once per unique row
@@ -27,8 +27,32 @@
 //   kStates                how many table-shaped fp32 state tensors;
 //   one(g, s, w, a)        the per-element update: g the summed, scaled
 //                          gradient, s[kStates] the states, w the weight.
-// AdagradRule (1 state) and FtrlRule (2 states) are instantiated; sparse
-// Adam / row-wise Adagrad are one more such struct plus entry points.
+// AdagradRule (1 state) and FtrlRule (2 states) are instantiated.  That
+// interface is per ELEMENT with table-shaped states: lazy Adam would be one
+// more such struct plus entry points; row-wise Adagrad is not.
+//
+// Row-wise Adagrad keeps ONE fp32 accumulator per row, state_row[rows]:
+//   m = (sum_c G[u, c]^2) / dim;  state_row[u] += m;
+//   table[u, :] -= lr * G[u, :] / (sqrt(state_row[u]) + eps).
+// It needs a reduction over the row before any element can move, and its
+// state is not shaped like its table, so it has pass-2 kernels of its own
+// (rowwise_adagrad_apply_kernel / _row_kernel below) on the same claim and
+// the same (row, quad) map, next to the element-wise template and sharing
+// only rule_elem (the wide companion) with it.  In the lane-sharing
+// kernel the row's dvec lanes complete the sum of squares with a
+// __shfl_xor butterfly (steps 1 .. dvec/2).  Every one of the row's lanes
+// then reads the old state_row[id] itself, rather than one lane reading it
+// and a shuffle broadcasting it: the lanes of a row share one address, so
+// the wave's load instruction asks for one 4-byte word per row either way,
+// it is issued together with the accumulator loads instead of behind
+// them, and a broadcast would put one more cross-lane operation and one
+// more wait on the path from the loads to the table store.  The butterfly
+// is symmetric (a + b == b + a at every step), so all lanes of a row hold
+// the same bits of the sum and of the new state; the quad-0 lane stores it.
+// The one-lane-per-row kernel makes two trips over the row: the first sums
+// the squares, the second re-reads the accumulator (the lane's own lines,
+// just fetched), zeroes it and applies the update; zeroing in the first
+// trip would lose G.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
@@ -195,6 +219,93 @@ __global__ void sparse_adagrad_apply_row_kernel(
   }
 }
 
+// ---- row-wise Adagrad -------------------------------------------------------
+
+// The (row, quad) map and claim of sparse_adagrad_apply_kernel.  Unlike
+// there, nobody leaves the iteration before the butterfly: every shuffle
+// is reached by all 64 lanes of the wave (losers and the inactive lanes of
+// a tail wave contribute zeros to their own rows' sums, which nobody uses),
+// so the loads sit inside `mine` and the shuffles outside it.  A row's
+// dvec lanes are contiguous and aligned to dvec, so lane ^ m for m < dvec
+// stays inside the row.
+template <typename WideRule>
+__global__ void rowwise_adagrad_apply_kernel(
+    float* __restrict__ table, float* __restrict__ state_row,
+    float* __restrict__ acc, float* __restrict__ wide_table,
+    StatePtrs<WideRule::kStates> wide_state, float* __restrict__ wide_acc,
+    int* __restrict__ stamp, const int64_t* __restrict__ ids,
+    int64_t n_rows, int dshift, int epoch, AdagradRule::Args a,
+    typename WideRule::Args wa) {
+  const int dvec = 1 << dshift;
+  const int64_t dim = (int64_t)dvec << 2;
+  const int64_t total = n_rows << dshift;
+  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  const int lane = threadIdx.x & 63;
+  const int c4 = threadIdx.x & (dvec - 1);
+  const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < total;
+       base += stride) {
+    const int64_t t = base + threadIdx.x;
+    const bool active = t < total;
+    int64_t id = 0;
+    int won = 0;
+    if (active) {
+      id = ids[t >> dshift];
+      if (c4 == 0) won = atomicExch(&stamp[id], epoch) != epoch;
+    }
+    won = __shfl(won, lane - c4);
+    const bool mine = active && won;
+    const int64_t q = (id * dim >> 2) + c4;
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    float s = 0.f;
+    if (mine) {
+      QuadIo<F32Io>::load4(acc, q, g);
+      QuadIo<F32Io>::store4(acc, q, zero);
+      s = state_row[id];
+    }
+    float ss = g[0] * g[0] + g[1] * g[1] + g[2] * g[2] + g[3] * g[3];
+    for (int m = 1; m < dvec; m <<= 1) ss += __shfl_xor(ss, m);
+    if (!mine) continue;
+    s += ss / (float)dim;
+    const float denom = sqrtf(s) + a.eps;
+    float w[4];
+    QuadIo<F32Io>::load4(table, q, w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] -= a.lr * g[j] / denom;
+    QuadIo<F32Io>::store4(table, q, w);
+    if (c4 == 0) {
+      state_row[id] = s;
+      if constexpr (WideRule::kStates > 0)
+        rule_elem<WideRule>(wide_acc, wide_state, wide_table, id, wa);
+    }
+  }
+}
+
+// One lane per update row, any dim (1, 7, 12, 512): two trips over the row.
+__global__ void rowwise_adagrad_apply_row_kernel(
+    float* __restrict__ table, float* __restrict__ state_row,
+    float* __restrict__ acc, int* __restrict__ stamp,
+    const int64_t* __restrict__ ids, int64_t n_rows, int64_t dim,
+    int epoch, AdagradRule::Args a) {
+  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       t < n_rows; t += stride) {
+    const int64_t id = ids[t];
+    if (atomicExch(&stamp[id], epoch) == epoch) continue;
+    const int64_t off = id * dim;
+    float ss = 0.f;
+    for (int64_t c = 0; c < dim; ++c) ss += acc[off + c] * acc[off + c];
+    const float s = state_row[id] + ss / (float)dim;
+    state_row[id] = s;
+    const float denom = sqrtf(s) + a.eps;
+    for (int64_t c = 0; c < dim; ++c) {
+      const float g = acc[off + c];
+      acc[off + c] = 0.f;
+      table[off + c] -= a.lr * g / denom;
+    }
+  }
+}
+
 // ---- host: checks -----------------------------------------------------------
 
 using Tensors = std::vector<torch::Tensor>;
@@ -206,6 +317,15 @@ void check_f32_like(const torch::Tensor& t, const torch::Tensor& table,
               t.numel() == table.numel(),
               name, " must be a contiguous fp32 GPU tensor shaped like "
               "its table");
+}
+
+// row-wise Adagrad's state: one value per table row, not per element
+void check_row_state(const torch::Tensor& t, const torch::Tensor& table) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+              t.scalar_type() == torch::kFloat32 &&
+              t.numel() == table.size(0),
+              "state_row must be a contiguous fp32 GPU tensor with one "
+              "value per table row");
 }
 
 void check_grad(const torch::Tensor& g, const char* name) {
@@ -356,6 +476,75 @@ FtrlRule::Args ftrl_args(double lr, double l1, double l2) {
   return {(float)lr, (float)l1, (float)l2};
 }
 
+// ---- row-wise Adagrad: checks and launches ----------------------------------
+
+void check_rowwise_apply(const torch::Tensor& table,
+                         const torch::Tensor& state_row,
+                         const torch::Tensor& acc,
+                         const torch::Tensor& stamp,
+                         const torch::Tensor& ids, int64_t epoch) {
+  check_apply(table, {}, acc, stamp, ids, epoch);
+  check_row_state(state_row, table);
+}
+
+void check_rowwise_apply_fused_wide(
+    const torch::Tensor& table, const torch::Tensor& state_row,
+    const torch::Tensor& acc, const torch::Tensor& wide_table,
+    const Tensors& wide_states, const torch::Tensor& wide_acc,
+    const torch::Tensor& stamp, const torch::Tensor& ids, int64_t epoch) {
+  check_apply_fused_wide(table, {}, acc, wide_table, wide_states, wide_acc,
+                         stamp, ids, epoch);
+  check_row_state(state_row, table);
+}
+
+void launch_rowwise_apply(torch::Tensor& table, torch::Tensor& state_row,
+                          torch::Tensor& acc, torch::Tensor& stamp,
+                          torch::Tensor& ids, int64_t epoch,
+                          AdagradRule::Args a) {
+  const int64_t dim = table.size(1);
+  const int64_t n = ids.numel();
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const int shift = quad_shift(dim);
+  if (shift >= 0) {
+    int grid = miyarn_grid_cap(n << shift, 8192);
+    hipLaunchKernelGGL(rowwise_adagrad_apply_kernel<NoRule>, dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       table.data_ptr<float>(), state_row.data_ptr<float>(),
+                       acc.data_ptr<float>(), (float*)nullptr,
+                       StatePtrs<0>{}, (float*)nullptr,
+                       stamp.data_ptr<int>(), ids.data_ptr<int64_t>(), n,
+                       shift, (int)epoch, a, NoRule::Args{});
+  } else {
+    int grid = miyarn_grid_cap(n, 8192);
+    hipLaunchKernelGGL(rowwise_adagrad_apply_row_kernel, dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       table.data_ptr<float>(), state_row.data_ptr<float>(),
+                       acc.data_ptr<float>(), stamp.data_ptr<int>(),
+                       ids.data_ptr<int64_t>(), n, dim, (int)epoch, a);
+  }
+}
+
+template <typename WideRule>
+void launch_rowwise_apply_fused_wide(
+    torch::Tensor& table, torch::Tensor& state_row, torch::Tensor& acc,
+    torch::Tensor& wide_table, const Tensors& wide_states,
+    torch::Tensor& wide_acc, torch::Tensor& stamp, torch::Tensor& ids,
+    int64_t epoch, AdagradRule::Args a, typename WideRule::Args wa) {
+  const int64_t n = ids.numel();
+  if (n == 0) return;
+  const int shift = quad_shift(table.size(1));
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  int grid = miyarn_grid_cap(n << shift, 8192);
+  hipLaunchKernelGGL(rowwise_adagrad_apply_kernel<WideRule>, dim3(grid),
+                     dim3(MIYARN_BLOCK), 0, stream,
+                     table.data_ptr<float>(), state_row.data_ptr<float>(),
+                     acc.data_ptr<float>(), wide_table.data_ptr<float>(),
+                     state_ptrs<WideRule::kStates>(wide_states),
+                     wide_acc.data_ptr<float>(), stamp.data_ptr<int>(),
+                     ids.data_ptr<int64_t>(), n, shift, (int)epoch, a, wa);
+}
+
 }  // namespace
 
 // ---- pass 2 alone (acc already holds the summed, scaled gradient) ---------
@@ -423,6 +612,47 @@ void sparse_ftrl_apply_fused_wide(
   launch_apply_fused_wide<FtrlRule, FtrlRule>(
       table, {accum, linear}, acc, wide_table, {wide_accum, wide_linear},
       wide_acc, stamp, ids, epoch, ftrl_args(lr, l1, l2),
+      ftrl_args(wide_lr, l1, l2));
+}
+
+// row-wise Adagrad, single table
+void sparse_rowwise_adagrad_apply(torch::Tensor table,
+                                  torch::Tensor state_row,
+                                  torch::Tensor acc, torch::Tensor stamp,
+                                  torch::Tensor ids, int64_t epoch,
+                                  double lr, double eps) {
+  check_rowwise_apply(table, state_row, acc, stamp, ids, epoch);
+  launch_rowwise_apply(table, state_row, acc, stamp, ids, epoch,
+                       adagrad_args(lr, eps));
+}
+
+// deep row-wise Adagrad + wide Adagrad, one (lr, eps)
+void sparse_rowwise_adagrad_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    int64_t epoch, double lr, double eps) {
+  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
+                                 {wide_state}, wide_acc, stamp, ids, epoch);
+  launch_rowwise_apply_fused_wide<AdagradRule>(
+      table, state_row, acc, wide_table, {wide_state}, wide_acc, stamp, ids,
+      epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
+}
+
+// deep row-wise Adagrad (lr, eps) + wide FTRL (wide_lr, l1, l2)
+void sparse_rowwise_adagrad_ftrl_apply_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, int64_t epoch, double lr, double eps,
+    double wide_lr, double l1, double l2) {
+  check_ftrl_args(wide_lr, l1, l2);
+  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
+                                 {wide_accum, wide_linear}, wide_acc, stamp,
+                                 ids, epoch);
+  launch_rowwise_apply_fused_wide<FtrlRule>(
+      table, state_row, acc, wide_table, {wide_accum, wide_linear},
+      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
       ftrl_args(wide_lr, l1, l2));
 }
 
@@ -538,5 +768,56 @@ void emb_bwd_ftrl_fused_wide(
   launch_apply_fused_wide<FtrlRule, FtrlRule>(
       table, {accum, linear}, acc, wide_table, {wide_accum, wide_linear},
       wide_acc, stamp, ids, epoch, ftrl_args(lr, l1, l2),
+      ftrl_args(wide_lr, l1, l2));
+}
+
+// Row-wise Adagrad on the unique ids u: G as above, m = sum_c G[u, c]^2 /
+// dim, state_row[u] += m, table[u, :] -= lr * G[u, :] / (sqrt(state_row[u])
+// + eps).
+void emb_bwd_rowwise_adagrad(torch::Tensor table, torch::Tensor state_row,
+                             torch::Tensor acc, torch::Tensor stamp,
+                             torch::Tensor ids, torch::Tensor grad,
+                             int64_t epoch, double lr, double eps,
+                             double scale) {
+  check_rowwise_apply(table, state_row, acc, stamp, ids, epoch);
+  check_deep_grad(table, ids, grad);
+  emb_bwd_dense(acc, ids, grad, scale);
+  launch_rowwise_apply(table, state_row, acc, stamp, ids, epoch,
+                       adagrad_args(lr, eps));
+}
+
+// deep row-wise Adagrad + wide Adagrad, shared flat ids
+void emb_bwd_rowwise_adagrad_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_state,
+    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
+    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
+    double eps, double scale) {
+  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
+                                 {wide_state}, wide_acc, stamp, ids, epoch);
+  check_pair_grads(table, ids, grad, gw);
+  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
+  launch_rowwise_apply_fused_wide<AdagradRule>(
+      table, state_row, acc, wide_table, {wide_state}, wide_acc, stamp, ids,
+      epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
+}
+
+// The recipe with a row-wise deep table: + wide FTRL, shared flat ids.
+void emb_bwd_rowwise_adagrad_ftrl_fused_wide(
+    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
+    torch::Tensor wide_table, torch::Tensor wide_accum,
+    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
+    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
+    double lr, double eps, double wide_lr, double l1, double l2,
+    double scale) {
+  check_ftrl_args(wide_lr, l1, l2);
+  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
+                                 {wide_accum, wide_linear}, wide_acc, stamp,
+                                 ids, epoch);
+  check_pair_grads(table, ids, grad, gw);
+  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
+  launch_rowwise_apply_fused_wide<FtrlRule>(
+      table, state_row, acc, wide_table, {wide_accum, wide_linear},
+      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
       ftrl_args(wide_lr, l1, l2));
 }
