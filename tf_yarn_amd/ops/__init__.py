@@ -955,6 +955,34 @@ def col_reduce_dot(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     return (x.float() * dy.float().unsqueeze(1)).sum(dim=0)
 
 
+def fused_head_grads_enabled() -> bool:
+    """MIYARN_FUSED_HEAD_GRADS=0 restores the separate kernels for a
+    single-logit head's own gradients: ``col_reduce_dot`` and its cast for
+    the weight, ``dl.sum()`` and its cast for the bias."""
+    return _env_switch_on("MIYARN_FUSED_HEAD_GRADS")
+
+
+def col_reduce_dot_sum(x: torch.Tensor, dy: torch.Tensor,
+                       out_dtype: torch.dtype = torch.float32):
+    """``(dw, db)`` of a single-logit head from ONE pass over ``x``:
+    ``dw[m] = sum_b dy[b] * x[b, m]`` as :func:`col_reduce_dot` computes
+    it and ``db [1] = sum_b dy[b]``, both summed in fp32 and stored as
+    ``out_dtype`` (fp32 or bf16, rounded once).  On the GPU the two are
+    views of one buffer."""
+    if _on_gpu(x, dy):
+        _require_ext()
+        if out_dtype in (torch.float32, torch.bfloat16):
+            dw, db = _C.col_reduce_dot_sum(x.contiguous(), dy.contiguous(),
+                                           out_dtype == torch.bfloat16)
+            return dw, db
+        dw, db = _C.col_reduce_dot_sum(x.contiguous(), dy.contiguous(),
+                                       False)
+        return dw.to(out_dtype), db.to(out_dtype)
+    dw = (x.float() * dy.float().unsqueeze(1)).sum(dim=0)
+    db = dy.float().sum().reshape(1)
+    return dw.to(out_dtype), db.to(out_dtype)
+
+
 def row_dot(x: torch.Tensor, w: torch.Tensor,
             bias: "torch.Tensor | None" = None) -> torch.Tensor:
     """y[b] = x[b] . w (+ bias): streaming GEMV for the single-logit
@@ -1004,6 +1032,11 @@ class ScalarHeadFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:  # input data (wide head) needs no dx
             dx = dy.unsqueeze(1) * weight.unsqueeze(0)
+        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] \
+                and _on_gpu(x, dy) and x.dtype == dy.dtype \
+                and fused_head_grads_enabled():
+            dw, db = col_reduce_dot_sum(x, dy, weight.dtype)
+            return dx, dw, db
         if ctx.needs_input_grad[1]:
             dw = col_reduce_dot(x, dy).to(weight.dtype)
         if ctx.needs_input_grad[2]:
@@ -1221,6 +1254,30 @@ def head_relu_bwd_db(dl: torch.Tensor, w_head: torch.Tensor,
     return dz, dz.sum(dim=0)
 
 
+def head_relu_bwd_grads(dl: torch.Tensor, w_head: torch.Tensor,
+                        y: torch.Tensor):
+    """:func:`head_relu_bwd_db` plus the head's own gradients,
+    ``(dz, dbias, dw_head, db_head)`` with ``dw_head = dl^T . y`` and
+    ``db_head [1] = dl.sum()`` (fp32 sums stored in ``y``'s dtype).  On the
+    GPU, bf16 widths the oct kernel takes run as ONE kernel over ``y`` and
+    one reduce for all three vectors; ``dz`` and ``dbias`` are
+    :func:`head_relu_bwd_db`'s to the bit.  Other GPU shapes compose
+    :func:`col_reduce_dot_sum` and :func:`head_relu_bwd_db`; the CPU runs
+    the reference pieces."""
+    if _on_gpu(dl, w_head, y) and HAVE_EXT and dl.dtype == y.dtype \
+            and w_head.dtype == y.dtype and y.dim() == 2 \
+            and y.size(1) % 4 == 0 and y.size(1) <= 8192 \
+            and y.dtype in (torch.float32, torch.bfloat16):
+        dz, dbias, dw_head, db_head = _C.head_relu_bwd_grads(
+            dl.contiguous(), w_head.contiguous(), y.contiguous(),
+            y.dtype == torch.bfloat16)
+        return dz, dbias, dw_head, db_head
+    dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
+    db_head = dl.sum().reshape(1).to(w_head.dtype)
+    dz, dbias = head_relu_bwd_db(dl, w_head, y)
+    return dz, dbias, dw_head, db_head
+
+
 class LinearBiasReLUHeadFn(torch.autograd.Function):
     """``relu(x @ w.T + bias) . w_head + b_head``: the last hidden layer
     and the single-logit head as ONE autograd node, so that backward goes
@@ -1251,11 +1308,15 @@ class LinearBiasReLUHeadFn(torch.autograd.Function):
         x, weight, y, w_head = ctx.saved_tensors
         dl = dl.contiguous()
         dw_head = db_head = None
-        if ctx.needs_input_grad[3]:
-            dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
-        if ctx.needs_input_grad[4]:
-            db_head = dl.sum().reshape(1).to(w_head.dtype)
-        dz, dbias = head_relu_bwd_db(dl, w_head, y)
+        if ctx.needs_input_grad[3] and ctx.needs_input_grad[4] \
+                and _on_gpu(dl, y) and fused_head_grads_enabled():
+            dz, dbias, dw_head, db_head = head_relu_bwd_grads(dl, w_head, y)
+        else:
+            if ctx.needs_input_grad[3]:
+                dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
+            if ctx.needs_input_grad[4]:
+                db_head = dl.sum().reshape(1).to(w_head.dtype)
+            dz, dbias = head_relu_bwd_db(dl, w_head, y)
         dx = dz.matmul(weight)
         kernel = _custom_wgrad_kernel(dz, x)
         if kernel is not None:

@@ -181,12 +181,21 @@ std::vector<torch::Tensor> head_relu_bwd_db(torch::Tensor dl,
                                             torch::Tensor w_head,
                                             torch::Tensor y,
                                             bool dbias_bf16);
+std::vector<torch::Tensor> head_relu_bwd_grads(torch::Tensor dl,
+                                               torch::Tensor w_head,
+                                               torch::Tensor y,
+                                               bool out_bf16);
 torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
+torch::Tensor reduce_tall(torch::Tensor part, bool out_bf16,
+                          int64_t quad_lanes);
 
 // lt_linear.hip
 torch::Tensor lt_linear(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias, bool relu);
 torch::Tensor col_reduce_dot(torch::Tensor x, torch::Tensor dy);
+std::vector<torch::Tensor> col_reduce_dot_sum(torch::Tensor x,
+                                              torch::Tensor dy,
+                                              bool out_bf16);
 torch::Tensor row_dot(torch::Tensor x, torch::Tensor w,
                       c10::optional<torch::Tensor> bias);
 std::vector<torch::Tensor> bce_head_fwd(torch::Tensor deep,
@@ -295,6 +304,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reduce_splitk", &reduce_splitk,
         "Split-K partial reduction with fused output cast",
         py::arg("part"), py::arg("out_bf16") = false);
+  m.def("reduce_tall", &reduce_tall,
+        "reduce_splitk's tall-slab kernel with 1 or 4 quad lanes per block",
+        py::arg("part"), py::arg("out_bf16") = false,
+        py::arg("quad_lanes") = 1);
   m.def("wgrad_nt", &wgrad_nt,
         "Split-K MFMA weight gradient: dW = dy^T @ x (bf16 in)",
         py::arg("dy"), py::arg("x"), py::arg("splitk"),
@@ -309,6 +322,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_bf16") = false);
   m.def("col_reduce_dot", &col_reduce_dot,
         "dw[m] = sum_b dy[b] * x[b,m] (single-logit head wgrad)");
+  m.def("col_reduce_dot_sum", &col_reduce_dot_sum,
+        "col_reduce_dot plus db = sum_b dy[b] from the same pass "
+        "(returns [dw, db])",
+        py::arg("x"), py::arg("dy"), py::arg("out_bf16") = false);
   m.def("row_dot", &row_dot,
         "y[b] = x[b].w + bias (single-logit head forward GEMV)");
   m.def("bce_head_fwd", &bce_head_fwd,
@@ -323,6 +340,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dl and w_head (no outer product; returns [dz, dbias])",
         py::arg("dl"), py::arg("w_head"), py::arg("y"),
         py::arg("dbias_bf16") = false);
+  m.def("head_relu_bwd_grads", &head_relu_bwd_grads,
+        "head_relu_bwd_db plus the head's own dw and db from the same pass "
+        "(returns [dz, dbias, dw_head, db_head])",
+        py::arg("dl"), py::arg("w_head"), py::arg("y"),
+        py::arg("out_bf16") = false);
   m.def("emb_fwd_into", &emb_fwd_into,
         "Embedding gather into a slice of a larger 2D buffer");
   m.def("emb_gather_sum", &emb_gather_sum,

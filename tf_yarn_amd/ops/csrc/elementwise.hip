@@ -9,6 +9,7 @@
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -165,20 +166,30 @@ __global__ void bias_relu_bwd_dbpart_kernel(
 // fp32 product, the bits torch's bf16 multiply stores.  Everything after
 // the load (mask, partial sums, their order) is shared, so dx and the
 // partial slab match the two-step path bit for bit.
+//
+// GRADS (HEAD only): the head's own gradients come out of the same pass.
+// The thread also keeps aw[j] += float(dl[r]) * float(y[r, j]) for every
+// row it visits, unmasked (dw_head = dl^T . y), and its oct-0 lane the
+// sum of dl (db_head).  The partial row grows to [2*cols + 4]: dbias in
+// columns [0, cols) exactly as before, dw_head in [cols, 2*cols), db_head
+// in column 2*cols (the last three are zero), so one reduce yields all
+// three vectors.
 __device__ __forceinline__ unsigned short bf16_mul_rne(float a, float b) {
   const float p = a * b;
   return p != p ? (unsigned short)0x7fc0 : f32_to_bf16(p);  // torch's NaN
 }
 
-template <bool HEAD>
+template <bool HEAD, bool GRADS = false>
 __device__ __forceinline__ void bias_relu_bwd_dbpart8_body(
     const unsigned short* __restrict__ dy,      // !HEAD
     const unsigned short* __restrict__ dl,      // HEAD: [rows]
     const unsigned short* __restrict__ w_head,  // HEAD: [cols]
     const unsigned short* __restrict__ y,
     unsigned short* __restrict__ dx,
-    float* __restrict__ dbias_part,  // [gridDim.x * rpb][cols]
+    float* __restrict__ dbias_part,  // [gridDim.x * rpb][pcols]
     int64_t rows, int64_t cols) {
+  static_assert(HEAD || !GRADS, "GRADS needs dl");
+  const int64_t pcols = GRADS ? 2 * cols + 4 : cols;
   const int octs = (int)(cols >> 3);
   const int rpb = blockDim.x / octs;       // row slots per block
   const int rid = threadIdx.x / octs;      // my slot
@@ -186,6 +197,9 @@ __device__ __forceinline__ void bias_relu_bwd_dbpart8_body(
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  float aw[8], sdl = 0.f;  // GRADS
+#pragma unroll
+  for (int j = 0; j < 8; ++j) aw[j] = 0.f;
   float wf[8];
   if (HEAD) {
     const bf16x8 wv = reinterpret_cast<const bf16x8*>(w_head)[q];
@@ -223,16 +237,28 @@ __device__ __forceinline__ void bias_relu_bwd_dbpart8_body(
               HEAD ? bf16_mul_rne(df[rr], wf[j]) : gv[rr][j];
           out[j] = keep ? g : (unsigned short)0;
           if (keep) acc[j] += bf16_to_f32(g);
+          if (GRADS) aw[j] += df[rr] * bf16_to_f32(yv[rr][j]);
         }
+        if (GRADS) sdl += df[rr];
         reinterpret_cast<bf16x8*>(dx)[(r0 + rr) * octs + q] = out;
       }
   }
-  float* part = dbias_part + slot * cols;
+  float* part = dbias_part + slot * pcols;
   f32x4 lo, hi;
 #pragma unroll
   for (int j = 0; j < 4; ++j) { lo[j] = acc[j]; hi[j] = acc[4 + j]; }
   reinterpret_cast<f32x4*>(part)[q * 2] = lo;
   reinterpret_cast<f32x4*>(part)[q * 2 + 1] = hi;
+  if (GRADS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lo[j] = aw[j]; hi[j] = aw[4 + j]; }
+    reinterpret_cast<f32x4*>(part + cols)[q * 2] = lo;
+    reinterpret_cast<f32x4*>(part + cols)[q * 2 + 1] = hi;
+    if (q == 0) {
+      const f32x4 sb = {sdl, 0.f, 0.f, 0.f};
+      reinterpret_cast<f32x4*>(part + 2 * cols)[0] = sb;
+    }
+  }
 }
 
 __global__ void bias_relu_bwd_dbpart8_kernel(
@@ -252,6 +278,16 @@ __global__ void head_relu_bwd_dbpart8_kernel(
     float* __restrict__ dbias_part, int64_t rows, int64_t cols) {
   bias_relu_bwd_dbpart8_body<true>(nullptr, dl, w_head, y, dx, dbias_part,
                                    rows, cols);
+}
+
+__global__ void head_relu_bwd_grads8_kernel(
+    const unsigned short* __restrict__ dl,
+    const unsigned short* __restrict__ w_head,
+    const unsigned short* __restrict__ y,
+    unsigned short* __restrict__ dx,
+    float* __restrict__ part, int64_t rows, int64_t cols) {
+  bias_relu_bwd_dbpart8_body<true, true>(nullptr, dl, w_head, y, dx, part,
+                                         rows, cols);
 }
 
 // dx = dy * (y > 0)
@@ -328,6 +364,83 @@ __global__ void reduce_splitk_kernel(
     float vv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) vv[j] = acc[j];
+    QuadIo<OIo>::store4(out, q, vv);
+  }
+}
+
+// The same sum for TALL slabs (the dbias / col_reduce_dot partials: S in
+// the thousands, nm a few hundred), where the kernel above would run
+// S-long dependent chains on a handful of blocks.  A block owns QL
+// adjacent column quads and spreads the rows over its 256 / QL row lanes:
+// lane rl adds rows rl, rl + RL, rl + 2 RL, ... in ascending order into
+// one f32x4 (TR_UNROLL independent 16-byte loads in flight; a row past S
+// adds 0.0f), a fixed xor butterfly folds the row lanes of a wave, and the
+// four wave results are added in wave order through LDS.  No atomics, no
+// hand-off between blocks, and the order of every column's sum depends on
+// S alone: not on nm, the column or the placement, so a wider slab that
+// carries the same columns (the head kernel's fold) gives them the same
+// bits.
+//
+// Which block owns which quads is a matter of speed only.  A block reads
+// 16 * QL bytes of every 128-byte line it touches, and blocks go to the 8
+// XCDs round robin, so with neighbouring quads in neighbouring blocks every
+// XCD's L2 fetched every line of the slab.  Block b therefore takes the
+// (b / 8)-th quad group of XCD (b % 8)'s contiguous share: the blocks that
+// share a line share an L2.
+#define TR_UNROLL 16
+#define TR_XCDS 8
+
+template <typename OIo, int QL>
+__global__ void reduce_tall_kernel(
+    const float* __restrict__ part,
+    typename OIo::scalar_t* __restrict__ out, int S, int64_t nm) {
+  constexpr int RL = MIYARN_BLOCK / QL;  // row lanes per block
+  const int ql = threadIdx.x % QL;
+  const int rl = threadIdx.x / QL;
+  const int64_t quads = nm >> 2;
+  // a bijection of [0, gridDim.x): XCD x owns a run of n / 8 groups, the
+  // first n % 8 XCDs one more
+  const int xcd = blockIdx.x % TR_XCDS;
+  const int per = gridDim.x / TR_XCDS, rem = gridDim.x % TR_XCDS;
+  const int group = xcd * per + min(xcd, rem) + blockIdx.x / TR_XCDS;
+  const int64_t q = (int64_t)group * QL + ql;
+  const bool live = q < quads;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(part) + q;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int s = rl; s < S; s += TR_UNROLL * RL) {
+      f32x4 v[TR_UNROLL];
+#pragma unroll
+      for (int u = 0; u < TR_UNROLL; ++u)
+        v[u] = s + u * RL < S ? p[(int64_t)(s + u * RL) * quads] : zero;
+#pragma unroll
+      for (int u = 0; u < TR_UNROLL; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += v[u][j];
+    }
+  }
+  // a + b == b + a to the bit, so both partners of every exchange hold
+  // the same value and lane ql of the wave ends with the wave's sum
+#pragma unroll
+  for (int off = 32; off >= QL; off >>= 1)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);
+  __shared__ f32x4 wsum[MIYARN_BLOCK / 64][QL];
+  const int lane = threadIdx.x & 63;
+  if (lane < QL) wsum[threadIdx.x >> 6][lane] = acc;
+  __syncthreads();
+  if (threadIdx.x < QL && live) {
+    f32x4 t = wsum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < MIYARN_BLOCK / 64; ++w) {
+      const f32x4 v = wsum[w][threadIdx.x];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] += v[j];
+    }
+    float vv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) vv[j] = t[j];
     QuadIo<OIo>::store4(out, q, vv);
   }
 }
@@ -439,6 +552,22 @@ torch::Tensor bias_relu_bwd(torch::Tensor dy, torch::Tensor y) {
 torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
 
 namespace {
+
+// reduce_splitk with the kernel picked as for a slab of inner size
+// plan_nm: a slab that carries another slab's columns plus extra ones
+// (the head kernel's fold) sums the shared columns in the same order.
+torch::Tensor reduce_partials(const torch::Tensor& part, bool out_bf16,
+                              int64_t plan_nm);
+
+// MIYARN_TALL_REDUCE=0 (or empty) restores torch's sum(0) + cast for tall
+// slabs, and the partial-row cap that went with it.  Read on every call:
+// one build, and one process, can A/B both.
+bool tall_reduce_enabled() {
+  const char* v = std::getenv("MIYARN_TALL_REDUCE");
+  return v == nullptr || !(v[0] == '\0' || (v[0] == '0' && v[1] == '\0'));
+}
+
+#define COL_REDUCE_MIN_GRID 256  // col_reduce_dot: one block per CU
 
 // Launch shape of the oct kernel.  bias_relu_bwd_db and head_relu_bwd_db
 // both take it from here: the row-to-partial map, and so every bit of
@@ -573,6 +702,54 @@ std::vector<torch::Tensor> head_relu_bwd_db(torch::Tensor dl,
   return {dz, reduce_splitk(part, dbias_bf16)};
 }
 
+std::vector<torch::Tensor> col_reduce_dot_sum(torch::Tensor x,
+                                              torch::Tensor dy,
+                                              bool out_bf16);
+
+// head_relu_bwd_db plus the head's own gradients from the same pass over
+// y and the same reduce: {dz, dbias, dw_head, db_head} with
+// dw_head[m] = sum_b dl[b] * y[b, m] and db_head = sum_b dl[b] (fp32 sums,
+// rounded once if out_bf16).  dz and dbias are head_relu_bwd_db's to the
+// bit: same map, same order, same columns of the slab.  The last three
+// are views of one buffer.  Widths the oct kernel does not take run the
+// existing pieces.
+std::vector<torch::Tensor> head_relu_bwd_grads(torch::Tensor dl,
+                                               torch::Tensor w_head,
+                                               torch::Tensor y,
+                                               bool out_bf16) {
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && y.dim() == 2,
+              "y must be a contiguous 2D GPU tensor");
+  const int64_t rows = y.size(0);
+  const int64_t cols = y.size(1);
+  TORCH_CHECK(dl.is_cuda() && dl.is_contiguous() && dl.numel() == rows &&
+              dl.scalar_type() == y.scalar_type(), "dl must be [rows]");
+  TORCH_CHECK(w_head.is_cuda() && w_head.is_contiguous() &&
+              w_head.numel() == cols &&
+              w_head.scalar_type() == y.scalar_type(),
+              "w_head must be [cols]");
+  const DbOctPlan plan = db_oct_plan(
+      y.scalar_type() == torch::kBFloat16, rows, cols);
+  if (!plan.ok || rows == 0) {
+    auto grads = col_reduce_dot_sum(y, dl, out_bf16);
+    auto dzdb = head_relu_bwd_db(dl, w_head, y, out_bf16);
+    return {dzdb[0], dzdb[1], grads[0], grads[1]};
+  }
+  auto dz = torch::empty_like(y);
+  auto part = torch::empty({plan.grid * plan.rpb, 2 * cols + 4},
+                           y.options().dtype(torch::kFloat32));
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL(head_relu_bwd_grads8_kernel, dim3(plan.grid),
+                     dim3(plan.block8), 0, stream,
+                     reinterpret_cast<unsigned short*>(dl.data_ptr()),
+                     reinterpret_cast<unsigned short*>(w_head.data_ptr()),
+                     reinterpret_cast<unsigned short*>(y.data_ptr()),
+                     reinterpret_cast<unsigned short*>(dz.data_ptr()),
+                     part.data_ptr<float>(), rows, cols);
+  auto out = reduce_partials(part, out_bf16, cols);
+  return {dz, out.narrow(0, 0, cols), out.narrow(0, cols, cols),
+          out.narrow(0, 2 * cols, 1)};
+}
+
 void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale) {
   TORCH_CHECK(src.is_cuda() && src.is_contiguous() &&
               dst.is_cuda() && dst.is_contiguous(), "GPU contiguous only");
@@ -603,13 +780,18 @@ namespace {
 // memory-bound column reduction (hipBLASLt runs this M=1-ish GEMM at
 // ~190 us for 33 MB; this kernel is a straight stream).  Atomic-free:
 // per-block partials + host-side sum, like bias_relu_bwd_dbpart.
-template <typename Io>
+// SUM: lane 0 of each slot also adds up the dy values it has loaded anyway
+// (db = sum_b dy[b]) and the partial row grows by one quad, [cols + 4]:
+// dw in columns [0, cols) as before, db in column cols, three zeros.
+template <typename Io, bool SUM>
 __global__ void col_reduce_dot_kernel(
     const typename Io::scalar_t* __restrict__ x,
     const typename Io::scalar_t* __restrict__ dy,
-    float* __restrict__ part,  // [gridDim.x * slots][cols]
+    float* __restrict__ part,  // [gridDim.x * slots][SUM ? cols + 4 : cols]
     int64_t rows, int64_t cols) {
   const int64_t quads = cols >> 2;
+  const int64_t pcols = SUM ? cols + 4 : cols;
+  float sdy = 0.f;  // SUM
   // 2D map for narrow inputs: when the quad count divides the block,
   // the block covers blockDim/quads row slots concurrently (a 64-thread
   // 1D map left the chip underfilled on the 256-wide head).
@@ -632,6 +814,10 @@ __global__ void col_reduce_dot_kernel(
 #pragma unroll
     for (int rr = 0; rr < DB_ROWS; ++rr)
       w[rr] = rr < nr ? Io::load(dy, r0 + rr) : 0.f;
+    if (SUM) {
+#pragma unroll
+      for (int rr = 0; rr < DB_ROWS; ++rr) sdy += w[rr];
+    }
     int k = 0;
     for (int64_t q = ltid; q < quads; q += tpq, ++k) {
       float v[DB_ROWS][4];
@@ -645,7 +831,7 @@ __global__ void col_reduce_dot_kernel(
           for (int j = 0; j < 4; ++j) acc[k][j] += w[rr] * v[rr][j];
     }
   }
-  float* prow = part + slot * cols;
+  float* prow = part + slot * pcols;
   int k = 0;
   for (int64_t q = ltid; q < quads; q += tpq, ++k) {
     f32x4 o;
@@ -653,11 +839,21 @@ __global__ void col_reduce_dot_kernel(
     for (int j = 0; j < 4; ++j) o[j] = acc[k][j];
     reinterpret_cast<f32x4*>(prow)[q] = o;
   }
+  if (SUM && ltid == 0) {
+    const f32x4 o = {sdy, 0.f, 0.f, 0.f};
+    reinterpret_cast<f32x4*>(prow)[quads] = o;
+  }
 }
 
 }  // namespace
 
-torch::Tensor col_reduce_dot(torch::Tensor x, torch::Tensor dy) {
+namespace {
+
+// The kernel above plus the reduce of its slab: [cols] (SUM: [cols + 4],
+// the caller slices dw and db out of it), fp32 or bf16.
+torch::Tensor col_reduce_dot_launch(const torch::Tensor& x,
+                                    const torch::Tensor& dy, bool sum,
+                                    bool out_bf16) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2,
               "x must be contiguous 2D on GPU");
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
@@ -674,25 +870,51 @@ torch::Tensor col_reduce_dot(torch::Tensor x, torch::Tensor dy) {
                     : static_cast<int>(std::min<int64_t>(
                           MIYARN_BLOCK, ((quads + 63) / 64) * 64));
   const int64_t slots = multi ? MIYARN_BLOCK / quads : 1;
+  // MIYARN_MAX_BLOCKS partial rows suited torch's sum, but left narrow
+  // inputs on MAX_BLOCKS / slots blocks (32 of 256 CUs at 16 columns).
+  // The tall reducer takes more rows: at least one block per CU.
+  const int64_t cap = std::max<int64_t>(
+      MIYARN_MAX_BLOCKS / slots,
+      tall_reduce_enabled() ? COL_REDUCE_MIN_GRID : 1);
   int grid = static_cast<int>(std::max<int64_t>(
       1, std::min<int64_t>((rows + slots * DB_ROWS - 1) / (slots * DB_ROWS),
-                           MIYARN_MAX_BLOCKS / slots)));
-  auto part = torch::empty({grid * slots, cols},
+                           cap)));
+  const int64_t pcols = sum ? cols + 4 : cols;
+  auto part = torch::empty({grid * slots, pcols},
                            x.options().dtype(torch::kFloat32));
+#define MIYARN_CRD_LAUNCH(IO, T, SUM)                                       \
+  hipLaunchKernelGGL((col_reduce_dot_kernel<IO, SUM>), dim3(grid),          \
+                     dim3(block), 0, stream,                                \
+                     reinterpret_cast<const T*>(x.data_ptr()),              \
+                     reinterpret_cast<const T*>(dy.data_ptr()),             \
+                     part.data_ptr<float>(), rows, cols)
   if (x.scalar_type() == torch::kFloat32) {
-    hipLaunchKernelGGL(col_reduce_dot_kernel<F32Io>, dim3(grid),
-                       dim3(block), 0, stream, x.data_ptr<float>(),
-                       dy.data_ptr<float>(), part.data_ptr<float>(),
-                       rows, cols);
+    if (sum) MIYARN_CRD_LAUNCH(F32Io, float, true);
+    else MIYARN_CRD_LAUNCH(F32Io, float, false);
   } else {
     TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "fp32/bf16 only");
-    hipLaunchKernelGGL(col_reduce_dot_kernel<Bf16Io>, dim3(grid),
-                       dim3(block), 0, stream,
-                       reinterpret_cast<unsigned short*>(x.data_ptr()),
-                       reinterpret_cast<unsigned short*>(dy.data_ptr()),
-                       part.data_ptr<float>(), rows, cols);
+    if (sum) MIYARN_CRD_LAUNCH(Bf16Io, unsigned short, true);
+    else MIYARN_CRD_LAUNCH(Bf16Io, unsigned short, false);
   }
-  return cols % 4 == 0 ? reduce_splitk(part, false) : part.sum(0);
+#undef MIYARN_CRD_LAUNCH
+  return reduce_partials(part, out_bf16, cols);
+}
+
+}  // namespace
+
+torch::Tensor col_reduce_dot(torch::Tensor x, torch::Tensor dy) {
+  return col_reduce_dot_launch(x, dy, false, false);
+}
+
+// col_reduce_dot with db = sum_b dy[b] from the same pass and the same
+// reduce: returns {dw [cols], db [1]}, two views of one buffer, fp32 or
+// (out_bf16) rounded to bf16 once at the end.
+std::vector<torch::Tensor> col_reduce_dot_sum(torch::Tensor x,
+                                              torch::Tensor dy,
+                                              bool out_bf16) {
+  const int64_t cols = x.size(-1);
+  auto out = col_reduce_dot_launch(x, dy, true, out_bf16);
+  return {out.narrow(0, 0, cols), out.narrow(0, cols, 1)};
 }
 
 namespace {
@@ -863,25 +1085,63 @@ torch::Tensor bce_head_bwd(torch::Tensor sig, torch::Tensor labels,
   return dl;
 }
 
-torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16) {
+namespace {
+
+// quad lanes per block of reduce_tall_kernel.  Measured at the step's
+// slabs (scripts/micro_tall_reduce.py): see docs/Kernels.md.
+#define TR_QUAD_LANES 1
+
+template <int QL>
+void reduce_tall_launch(const torch::Tensor& part, torch::Tensor& out,
+                        int S, int64_t nm) {
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const int grid = static_cast<int>((nm / 4 + QL - 1) / QL);
+  if (out.scalar_type() == torch::kBFloat16) {
+    hipLaunchKernelGGL((reduce_tall_kernel<Bf16Io, QL>), dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       part.data_ptr<float>(),
+                       reinterpret_cast<unsigned short*>(out.data_ptr()),
+                       S, nm);
+  } else {
+    hipLaunchKernelGGL((reduce_tall_kernel<F32Io, QL>), dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       part.data_ptr<float>(), out.data_ptr<float>(),
+                       S, nm);
+  }
+}
+
+torch::Tensor reduce_out_like(const torch::Tensor& part, bool out_bf16) {
+  auto sizes = part.sizes().vec();
+  sizes.erase(sizes.begin());
+  return torch::empty(sizes, part.options().dtype(
+      out_bf16 ? torch::kBFloat16 : torch::kFloat32));
+}
+
+torch::Tensor reduce_partials(const torch::Tensor& part, bool out_bf16,
+                              int64_t plan_nm) {
   TORCH_CHECK(part.is_cuda() && part.is_contiguous() && part.dim() >= 2 &&
-              part.scalar_type() == torch::kFloat32, "bad partials");
+              part.scalar_type() == torch::kFloat32 && part.size(0) > 0,
+              "bad partials");
   const int S = static_cast<int>(part.size(0));
   const int64_t nm = part.numel() / S;
   TORCH_CHECK(nm % 4 == 0, "reduce_splitk needs inner numel %% 4 == 0");
-  if (S > 64 || nm < 4 * MIYARN_BLOCK) {
+  TORCH_CHECK(part.size(0) < (1 << 30) && nm / 4 < (1LL << 31),
+              "slab too large");
+  if (S > 64 || plan_nm < 4 * MIYARN_BLOCK) {
     // The vectorized kernel parallelizes over the inner dim only; deep
     // stacks of narrow partials (the dbias case: S up to 8192, nm 256)
     // would serialize S-long latency chains on a handful of blocks
-    // (measured 4x whole-step regression).  torch's tree reduce is the
-    // right shape there.
-    auto out = part.sum(0);
-    return out_bf16 ? out.to(torch::kBFloat16) : out;
+    // (measured 4x whole-step regression).  Those go to the tall kernel,
+    // which spreads the rows over the lanes of a block.
+    if (!tall_reduce_enabled()) {
+      auto out = part.sum(0);
+      return out_bf16 ? out.to(torch::kBFloat16) : out;
+    }
+    auto out = reduce_out_like(part, out_bf16);
+    reduce_tall_launch<TR_QUAD_LANES>(part, out, S, nm);
+    return out;
   }
-  auto sizes = part.sizes().vec();
-  sizes.erase(sizes.begin());
-  auto out = torch::empty(sizes, part.options().dtype(
-      out_bf16 ? torch::kBFloat16 : torch::kFloat32));
+  auto out = reduce_out_like(part, out_bf16);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int grid = miyarn_grid(nm / 4);
   if (out_bf16) {
@@ -896,5 +1156,30 @@ torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16) {
                        part.data_ptr<float>(), out.data_ptr<float>(),
                        S, nm);
   }
+  return out;
+}
+
+}  // namespace
+
+torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16) {
+  TORCH_CHECK(part.dim() >= 2 && part.size(0) > 0, "bad partials");
+  return reduce_partials(part, out_bf16, part.numel() / part.size(0));
+}
+
+// The tall kernel on any slab with a chosen number of quad lanes per
+// block (1 or 4): for tests and scripts/micro_tall_reduce.py.
+torch::Tensor reduce_tall(torch::Tensor part, bool out_bf16,
+                          int64_t quad_lanes) {
+  TORCH_CHECK(part.is_cuda() && part.is_contiguous() && part.dim() >= 2 &&
+              part.scalar_type() == torch::kFloat32 && part.size(0) > 0 &&
+              part.size(0) < (1 << 30), "bad partials");
+  const int S = static_cast<int>(part.size(0));
+  const int64_t nm = part.numel() / S;
+  TORCH_CHECK(nm % 4 == 0 && nm / 4 < (1LL << 31),
+              "reduce_tall needs inner numel %% 4 == 0");
+  auto out = reduce_out_like(part, out_bf16);
+  if (quad_lanes == 1) reduce_tall_launch<1>(part, out, S, nm);
+  else if (quad_lanes == 4) reduce_tall_launch<4>(part, out, S, nm);
+  else TORCH_CHECK(false, "quad_lanes must be 1 or 4");
   return out;
 }
