@@ -180,7 +180,10 @@ class _ShardedLookup(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, deep_table, wide_table, module, ids, deep_out_buf,
-                col_offset, dense=None):
+                col_offset, dense=None, grad_enabled=False):
+        # grad_enabled: the caller's grad mode (autograd has switched it
+        # off in here); a permutation is prefetched only for a forward
+        # that a backward can follow
         m: "ShardedCriteoEmbeddings" = module
         W, B = m.world, ids.shape[0]
         D = m.dim
@@ -204,7 +207,7 @@ class _ShardedLookup(torch.autograd.Function):
                 ctx.raw_ids = True
             else:
                 saved = (ids + m.full_offsets.unsqueeze(0)).reshape(-1)
-                m._start_perm_async(saved)
+                m._start_perm_async(saved, grad_enabled)
             ctx.module = m
             ctx.save_for_backward(saved)
             ctx.local_only = True
@@ -220,7 +223,7 @@ class _ShardedLookup(torch.autograd.Function):
             ops.emb_fwd_into(deep_table, flat, deep_out_buf, col_offset)
             wide_out = ops.emb_gather_sum(wide_table, flat.reshape(B, -1),
                                           m.out_bf16)
-            m._start_perm_async(flat)
+            m._start_perm_async(flat, grad_enabled)
             ctx.module = m
             ctx.save_for_backward(flat)
             ctx.local_only = True
@@ -240,7 +243,7 @@ class _ShardedLookup(torch.autograd.Function):
         # local row offsets: layout [peer][b][j], j = feature slot
         flat_local = ids_recv + m.own_offsets_tiled[:ids_recv.numel()]
 
-        m._start_perm_async(flat_local)
+        m._start_perm_async(flat_local, grad_enabled)
 
         # ---- owner-local gathers ----------------------------------------
         vec = ops.emb_fwd(deep_table, flat_local, m.out_bf16)  # [W*n_own, D]
@@ -301,7 +304,7 @@ class _ShardedLookup(torch.autograd.Function):
                 m._raw_ids_keys.add(flat_ids.data_ptr())
             m._deep_sink.append((flat_ids, emb_grad))
             m._wide_sink.append((flat_ids, grad_wide.contiguous()))
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         B = ctx.B
         n_own = B * m.f_own
         # route deep grads to owners: send chunk for owner s = the
@@ -327,7 +330,7 @@ class _ShardedLookup(torch.autograd.Function):
         with commprobe.span("ag_wide"):
             dist.all_gather_into_tensor(gw_all, gw, group=m.group)
         m._wide_sink.append((flat_ids, gw_all))
-        return None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None
 
 
 class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
@@ -442,7 +445,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             self._ensure_tiled(ids.numel(), ids.device)
         out_buf, wide = _ShardedLookup.apply(
             self.weight, self.wide_weight, self, ids, deep_out_buf,
-            col_offset, dense)
+            col_offset, dense, torch.is_grad_enabled())
         return out_buf, wide
 
     def _fused_lookup_ok(self, ids, dense, deep_out_buf,
@@ -458,8 +461,8 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         """Whether this step's update will be the fused deep+wide SGD
         scatter, which takes raw ``[B, F]`` ids plus ``full_offsets``:
         both tables on SGD at one lr, and not the binned scatter.  In
-        the auto mode the one-time skew probe looks at flat ids when the
-        first update is applied; until it has decided, flat ids are
+        the auto mode the one-time skew probe looks at the flat ids of the
+        first training forward; until it has decided, flat ids are
         kept."""
         if self._stateful() or self.wide_sparse_lr is not None \
                 or self.dim % 4 != 0:
@@ -496,15 +499,21 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             return
         self._apply_pending(lr)
 
-    def _start_perm_async(self, flat_ids: torch.Tensor) -> None:
+    def _start_perm_async(self, flat_ids: torch.Tensor,
+                          grad_enabled: bool) -> None:
         """Kick off the binned-scatter permutation (pass A) on a side
         stream DURING FORWARD: it depends only on the ids, and its
         ~200 us of latency/atomic-bound work hides under the MFMA-bound
-        MLP GEMMs instead of sitting on the backward critical path."""
+        MLP GEMMs instead of sitting on the backward critical path.
+        ``grad_enabled`` is the grad mode of the module's forward call
+        (inside ``_ShardedLookup.forward`` autograd has switched it off):
+        only a forward that a backward can follow starts one.  An older
+        permutation that was never applied is dropped."""
+        self._pending_perm = None
         if self._stateful():
             return  # the binned scatter is an SGD kernel
         if not (flat_ids.is_cuda and self.dim == 16 and ops.HAVE_EXT
-                and torch.is_grad_enabled() and self._binned_on(flat_ids)):
+                and grad_enabled and self._binned_on(flat_ids)):
             return
         rb = ops.pick_region_bits(self.weight.shape[0], flat_ids.numel())
         if not _perm_stream_enabled():
@@ -665,8 +674,11 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             key, perm, ev = self._pending_perm
             if ev is not None:
                 torch.cuda.current_stream().wait_event(ev)
-                for t in perm:
-                    t.record_stream(torch.cuda.current_stream())
+            # built on the side stream or (inline) on the forward's, used
+            # on this one, which may be the caller's ``stream=``: keep the
+            # allocator from handing the blocks out while pass B reads them
+            for t in perm:
+                t.record_stream(torch.cuda.current_stream())
             perms[key] = perm
             self._pending_perm = None
 
@@ -740,3 +752,5 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         self._deep_sink.clear()
         self._wide_sink.clear()
         self._raw_ids_keys.clear()
+        # matched to its ids by address: must not outlive them
+        self._pending_perm = None

@@ -278,7 +278,7 @@ def emb_scatter_sum_binned(table: torch.Tensor, ids: torch.Tensor,
     """Binned replacement for :func:`emb_scatter_sum` (scalar wide
     tables): grad for flat update j is ``grad[j // F]``."""
     n = ids.numel()
-    g_div = n // grad.numel()
+    g_div = n // grad.numel() if grad.numel() else 1  # empty update
     if not _on_gpu(table, ids, grad):
         expanded = grad.float().reshape(-1, 1).expand(-1, g_div) \
             .reshape(-1)

@@ -160,6 +160,7 @@ void emb_bwd_rowwise_adagrad_ftrl_fused_wide(
     double scale);
 
 // binned_scatter.hip
+py::dict binned_layout();
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
                                               int64_t n_rows,
                                               int64_t region_bits);
@@ -349,6 +350,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Embedding gather into a slice of a larger 2D buffer");
   m.def("emb_gather_sum", &emb_gather_sum,
         "Wide-part gather-sum: out[b] = sum_f table[ids[b,f]]");
+  m.def("binned_layout", &binned_layout,
+        "Layout constants of the binned scatter (hash capacities, probe "
+        "limit, hash threshold, launch shapes)");
   m.def("binned_permutation", &binned_permutation,
         "Region-binned permutation of sparse update indices");
   m.def("emb_bwd_sgd_binned", &emb_bwd_sgd_binned,

@@ -51,6 +51,12 @@ constexpr int kHashDeep = 1024;   // slots; 1024*(4 + 17*4) B = 72 KB LDS
 constexpr int kValStride = 17;    // bank-conflict-free value stride
 constexpr int kHashScalar = 2048; // slots; 2048*(4+4) B = 16 KB LDS
 constexpr int kProbeMax = 64;
+constexpr uint32_t kHashMul = 2654435761u;  // odd: bijective on 2^k rows
+// a bin takes the LDS hash while count <= kLoadNum / kLoadDen of capacity
+constexpr int kLoadNum = 3, kLoadDen = 4;
+constexpr int kHashMaxDeep = (kLoadNum * kHashDeep) / kLoadDen;
+constexpr int kHashMaxScalar = (kLoadNum * kHashScalar) / kLoadDen;
+constexpr int kApplyGridMax = 8192;  // pass B blocks; grid-stride over bins
 constexpr int kJBits = 31;
 constexpr int64_t kJMask = (int64_t{1} << kJBits) - 1;
 
@@ -105,7 +111,7 @@ __global__ void bin_slot_kernel(const int64_t* __restrict__ ids,
 }
 
 __device__ __forceinline__ int hash_slot(int32_t key, int capacity) {
-  return static_cast<int>((static_cast<uint32_t>(key) * 2654435761u)
+  return static_cast<int>((static_cast<uint32_t>(key) * kHashMul)
                           & (capacity - 1));
 }
 
@@ -147,7 +153,7 @@ __global__ void binned_apply_deep_kernel(
     const int start = starts[bin], end = starts[bin + 1];
     const int count = end - start;
     if (count == 0) continue;
-    const bool use_hash = count <= (3 * kHashDeep) / 4;
+    const bool use_hash = count <= kHashMaxDeep;
     for (int k = start + threadIdx.x; k < end; k += blockDim.x) {
       const int64_t packed = order[k];
       const int64_t j = packed & kJMask;
@@ -218,7 +224,7 @@ __global__ void binned_apply_scalar_kernel(
     const int start = starts[bin], end = starts[bin + 1];
     const int count = end - start;
     if (count == 0) continue;
-    const bool use_hash = count <= (3 * kHashScalar) / 4;
+    const bool use_hash = count <= kHashMaxScalar;
     for (int k = start + threadIdx.x; k < end; k += blockDim.x) {
       const int64_t packed = order[k];
       const int64_t j = packed & kJMask;
@@ -249,6 +255,25 @@ __global__ void binned_apply_scalar_kernel(
 }
 
 }  // namespace
+
+// The layout constants above, for tests that aim at one branch (the hash
+// threshold, the probe limit, the wrap): no GPU work.
+py::dict binned_layout() {
+  py::dict d;
+  d["hash_deep"] = kHashDeep;
+  d["hash_scalar"] = kHashScalar;
+  d["hash_max_count_deep"] = kHashMaxDeep;
+  d["hash_max_count_scalar"] = kHashMaxScalar;
+  d["probe_max"] = kProbeMax;
+  d["hash_mul"] = kHashMul;
+  d["j_bits"] = kJBits;
+  d["scan_block"] = kScanBlock;
+  d["apply_block"] = MIYARN_BLOCK;
+  d["apply_grid_max"] = kApplyGridMax;
+  d["perm_block"] = MIYARN_BLOCK;
+  d["perm_grid_max"] = MIYARN_MAX_BLOCKS;
+  return d;
+}
 
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
                                               int64_t n_rows,
@@ -302,7 +327,7 @@ void emb_bwd_sgd_binned(torch::Tensor table, torch::Tensor ids,
               starts.scalar_type() == torch::kInt32, "bad perm dtypes");
   const int n_bins = static_cast<int>(starts.numel() - 1);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int grid = std::min(n_bins, 8192);
+  const int grid = std::min(n_bins, kApplyGridMax);
   const float nls = static_cast<float>(-lr * scale);
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL((binned_apply_deep_kernel<F32Io, 16>), dim3(grid),
@@ -334,7 +359,7 @@ void emb_scatter_sum_binned(torch::Tensor table, torch::Tensor ids,
               starts.scalar_type() == torch::kInt32, "bad perm dtypes");
   const int n_bins = static_cast<int>(starts.numel() - 1);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int grid = std::min(n_bins, 8192);
+  const int grid = std::min(n_bins, kApplyGridMax);
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(binned_apply_scalar_kernel<F32Io>, dim3(grid),
                        dim3(MIYARN_BLOCK), 0, stream,
