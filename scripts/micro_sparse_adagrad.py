@@ -39,6 +39,9 @@ F = 26
 DIM = 16
 LR, EPS = 0.01, 1e-10
 L1, L2 = 0.001, 0.001  # FTRL
+# --rule's names -> the ops' rule names
+RULE_NAMES = {"adagrad": "adagrad", "ftrl": "ftrl",
+              "rowwise": "rowwise_adagrad"}
 
 
 def timed(fn, iters, repeats):
@@ -161,78 +164,33 @@ def main():
         print(f"{name:32s} {med:8.1f} us  ({lo:.1f} .. {hi:.1f})",
               flush=True)
 
-    if args.rule == "adagrad":
-        def pass2():
-            C.sparse_adagrad_apply_fused_wide(
-                table, states[0], ws.acc, wide, wide_states[0],
-                ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
+    def side(rule, tbl, sts, g):
+        """One table's side under `rule`, this script's name for it."""
+        return ops.SparseSide(RULE_NAMES[rule], tbl, tuple(sts), g, LR, EPS,
+                              L1, L2)
 
-        def total():
-            ops.emb_bwd_adagrad_fused_wide(
-                table, states[0], wide, wide_states[0], ids, grad, gw,
-                lr=LR, eps=EPS, workspace=ws)
-    elif args.rule == "ftrl":
-        def pass2():
-            C.sparse_ftrl_apply_fused_wide(
-                table, *states, ws.acc, wide, *wide_states, ws.wide_acc,
-                ws.stamp, ids, ws.next_epoch(), LR, LR, L1, L2)
+    def pass2_of(deep_rule, deep_states):
+        """Pass 2 alone, straight on the C++ entry: sides without
+        gradients, the wide companion whenever --rule has one."""
+        def c_side(rule, tbl, sts, acc):
+            return (RULE_NAMES[rule], tbl, list(sts), acc, None, LR, EPS,
+                    L1, L2)
+        d = c_side(deep_rule, table, deep_states, ws.acc)
+        w = c_side(rules[1], wide, wide_states, ws.wide_acc) if pair \
+            else None
+        return lambda: C.emb_bwd_sparse(d, w, ws.stamp, ids,
+                                        ws.next_epoch(), 1.0)
 
-        def total():
-            ops.emb_bwd_ftrl_fused_wide(
-                table, *states, wide, *wide_states, ids, grad, gw, lr=LR,
-                l1=L1, l2=L2, workspace=ws)
-    elif args.rule == "rowwise":
-        def pass2():
-            C.sparse_rowwise_adagrad_apply(
-                table, states[0], ws.acc, ws.stamp, ids, ws.next_epoch(),
-                LR, EPS)
+    def update(workspace=ws, **sides):
+        """The public op; the sides are built per call, as the
+        emb_bwd_<rule>* wrappers build them."""
+        return lambda: ops.emb_bwd_sparse(
+            ids, workspace=workspace,
+            **{k: side(*v) for k, v in sides.items()})
 
-        def total():
-            ops.emb_bwd_rowwise_adagrad(table, states[0], ids, grad, lr=LR,
-                                        eps=EPS, workspace=ws)
-    elif args.rule == "rowwise+adagrad":
-        def pass2():
-            C.sparse_rowwise_adagrad_apply_fused_wide(
-                table, states[0], ws.acc, wide, wide_states[0],
-                ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
-
-        def total():
-            ops.emb_bwd_rowwise_adagrad_fused_wide(
-                table, states[0], wide, wide_states[0], ids, grad, gw,
-                lr=LR, eps=EPS, workspace=ws)
-    elif args.rule == "rowwise+ftrl":
-        def pass2():
-            C.sparse_rowwise_adagrad_ftrl_apply_fused_wide(
-                table, states[0], ws.acc, wide, *wide_states, ws.wide_acc,
-                ws.stamp, ids, ws.next_epoch(), LR, EPS, LR, L1, L2)
-
-        def total():
-            ops.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-                table, states[0], wide, *wide_states, ids, grad, gw,
-                lr=LR, eps=EPS, l1=L1, l2=L2, workspace=ws)
-    else:
-        def pass2():
-            C.sparse_adagrad_ftrl_apply_fused_wide(
-                table, states[0], ws.acc, wide, *wide_states, ws.wide_acc,
-                ws.stamp, ids, ws.next_epoch(), LR, EPS, LR, L1, L2)
-
-        def total():
-            ops.emb_bwd_adagrad_ftrl_fused_wide(
-                table, states[0], wide, *wide_states, ids, grad, gw,
-                lr=LR, eps=EPS, l1=L1, l2=L2, workspace=ws)
-
-    def single(rule, tbl, sts, g, workspace, wide_table):
-        if rule == "rowwise":
-            return lambda: ops.emb_bwd_rowwise_adagrad(
-                tbl, sts[0], ids, g, lr=LR, eps=EPS, workspace=workspace)
-        if rule == "adagrad":
-            fn = ops.emb_bwd_adagrad_wide if wide_table \
-                else ops.emb_bwd_adagrad
-            return lambda: fn(tbl, sts[0], ids, g, lr=LR, eps=EPS,
-                              workspace=workspace)
-        fn = ops.emb_bwd_ftrl_wide if wide_table else ops.emb_bwd_ftrl
-        return lambda: fn(tbl, *sts, ids, g, lr=LR, l1=L1, l2=L2,
-                          workspace=workspace)
+    deep_side = (rules[0], table, states, grad)
+    wide_side = (rules[1], wide, wide_states, gw) if pair else None
+    pass2 = pass2_of(rules[0], states)
 
     record("sgd_fused_wide", lambda: C.emb_bwd_sgd_fused_wide(
         table, wide, ids, grad, gw, LR, 1.0))
@@ -247,41 +205,29 @@ def main():
     record(f"{tag}_pass2_claim_apply", pass2)
     assert not ws.acc.any() and not ws.wide_acc.any()
     if pair:
-        record(f"{tag}_fused_wide_total", total)
-        record(f"{tag}_deep_only",
-               single(rules[0], table, states, grad, ws, False))
-        record(f"{tag}_wide_only", single(rules[1], wide, wide_states, gw,
-                                          ws.wide_view(), True))
+        record(f"{tag}_fused_wide_total",
+               update(deep=deep_side, wide=wide_side))
+        record(f"{tag}_deep_only", update(deep=deep_side))
+        record(f"{tag}_wide_only",
+               update(workspace=ws.wide_view(), wide=wide_side))
         if rules[0] == "rowwise":
             # the element-wise pair with the same wide rule on the same
             # tables, same process: figures of two processes differ by more
             # than the rules do
             elem = torch.zeros_like(table)
-            if rules[1] == "adagrad":
-                def elem_pass2():
-                    C.sparse_adagrad_apply_fused_wide(
-                        table, elem, ws.acc, wide, wide_states[0],
-                        ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR, EPS)
-            else:
-                def elem_pass2():
-                    C.sparse_adagrad_ftrl_apply_fused_wide(
-                        table, elem, ws.acc, wide, *wide_states,
-                        ws.wide_acc, ws.stamp, ids, ws.next_epoch(), LR,
-                        EPS, LR, L1, L2)
+            elem_pass2 = pass2_of("adagrad", [elem])
             record("elementwise_pair_pass2_claim_apply", elem_pass2)
             record(f"{tag}_pass2_claim_apply_again", pass2)
             record("elementwise_pair_pass2_claim_apply_again", elem_pass2)
             del elem
     else:
-        record(f"{tag}_total", total)
+        record(f"{tag}_total", update(deep=deep_side))
         # element-wise Adagrad on the same deep table, same process
         elem = torch.zeros_like(table)
         record("adagrad_deep_pass2_claim_apply",
-               lambda: C.sparse_adagrad_apply(
-                   table, elem, ws.acc, ws.stamp, ids, ws.next_epoch(), LR,
-                   EPS))
+               pass2_of("adagrad", [elem]))
         record("adagrad_deep_total",
-               single("adagrad", table, [elem], grad, ws, False))
+               update(deep=("adagrad", table, [elem], grad)))
         record(f"{tag}_pass2_claim_apply_again", pass2)
         del elem
     record("torch_unique_index_add", lambda: torch_baseline(

@@ -8,6 +8,8 @@ sqrt/div rounding, the class of difference the dense Adagrad kernel test
 (``test_fused_adagrad_adadelta_gpu_vs_torch``) covers with
 ``torch.allclose(..., atol=1e-5)``; the same call is used here."""
 
+import collections
+
 import pytest
 import torch
 
@@ -154,12 +156,14 @@ def test_fused_deep_wide(g_div, dim, mixed):
 
 
 class _Counted:
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
+    """``_C.emb_bwd_sparse``, counting calls by (deep rule, wide rule)."""
 
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
+    def __init__(self, fn):
+        self.fn, self.calls = fn, collections.Counter()
+
+    def __call__(self, deep, wide, *args):
+        self.calls[(deep and deep[0], wide and wide[0])] += 1
+        return self.fn(deep, wide, *args)
 
 
 @pytest.mark.parametrize("sharded", [False, True])
@@ -170,11 +174,8 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
                         hidden=(64, 32), compute_dtype=torch.bfloat16,
                         sharded=sharded,
                         sparse_optimizer="adagrad").cuda()
-    counted = {name: _Counted(getattr(ops._C, name))
-               for name in ("emb_bwd_adagrad", "emb_bwd_adagrad_wide",
-                            "emb_bwd_adagrad_fused_wide")}
-    for name, c in counted.items():
-        monkeypatch.setattr(ops._C, name, c)
+    counted = _Counted(ops._C.emb_bwd_sparse)
+    monkeypatch.setattr(ops._C, "emb_bwd_sparse", counted)
     if sharded:
         e = model.embeddings
         params = (e.weight, e.state_sum, e.wide_weight, e.wide_state_sum)
@@ -197,13 +198,17 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
         for got, want in zip(params, (dt, ds, wt, wst)):
             assert _close(got.detach(), want), step
     if sharded:
-        assert counted["emb_bwd_adagrad_fused_wide"].calls == 2
+        assert counted.calls == {("adagrad", "adagrad"): 2}
     else:
-        assert counted["emb_bwd_adagrad"].calls == 2
-        assert counted["emb_bwd_adagrad_wide"].calls == 2
+        assert counted.calls == {("adagrad", None): 2, (None, "adagrad"): 2}
     for name, buf in model.named_buffers():
         if "state_sum" in name or "_adagrad" in name:
             assert buf.is_cuda and getattr(buf, "_miyarn_sharded", False)
+
+
+def _side(table, state, acc, grad):
+    """An Adagrad side as ``_C.emb_bwd_sparse`` takes it."""
+    return ("adagrad", table, [state], acc, grad, LR, 1e-10, 0.0, 0.0)
 
 
 def test_bad_inputs_raise_before_any_launch():
@@ -216,8 +221,8 @@ def test_bad_inputs_raise_before_any_launch():
 
     def call(table=table, state=state, acc=ws.acc, stamp=ws.stamp, ids=ids,
              grad=grad):
-        ops._C.emb_bwd_adagrad(table, state, acc, stamp, ids, grad, 1,
-                               LR, 1e-10, 1.0)
+        ops._C.emb_bwd_sparse(_side(table, state, acc, grad), None, stamp,
+                              ids, 1, 1.0)
 
     bad = [
         dict(grad=grad.half()),                       # dtype
@@ -239,14 +244,16 @@ def test_bad_inputs_raise_before_any_launch():
     wide = torch.zeros(50, 1).cuda()
     wws = ops.SparseAdagradWorkspace(table, wide)
     with pytest.raises(RuntimeError):  # gw dtype differs from grad's
-        ops._C.emb_bwd_adagrad_fused_wide(
-            table, state, wws.acc, wide, torch.zeros_like(wide),
-            wws.wide_acc, wws.stamp, ids, grad,
-            torch.ones(10, dtype=torch.bfloat16).cuda(), 1, LR, 1e-10, 1.0)
+        ops._C.emb_bwd_sparse(
+            _side(table, state, wws.acc, grad),
+            _side(wide, torch.zeros_like(wide), wws.wide_acc,
+                  torch.ones(10, dtype=torch.bfloat16).cuda()),
+            wws.stamp, ids, 1, 1.0)
     with pytest.raises(RuntimeError):  # 40 ids, 7 examples
-        ops._C.emb_bwd_adagrad_wide(
-            wide, torch.zeros_like(wide), wws.wide_acc, wws.stamp, ids,
-            torch.ones(7).cuda(), 1, LR, 1e-10, 1.0)
+        ops._C.emb_bwd_sparse(
+            None, _side(wide, torch.zeros_like(wide), wws.wide_acc,
+                        torch.ones(7).cuda()),
+            wws.stamp, ids, 1, 1.0)
     torch.cuda.synchronize()
     assert torch.equal(table, t0)
     assert not state.any() and not ws.acc.any() and not ws.stamp.any()

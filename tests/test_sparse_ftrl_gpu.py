@@ -16,6 +16,8 @@ sides, except for elements whose ``| |z'| - l1 |`` is below 1e-4 on the
 CPU (the weight is continuous through 0 there); at most 1% of the touched
 elements may be excused this way, asserted on the reference."""
 
+import collections
+
 import pytest
 import torch
 
@@ -203,12 +205,14 @@ def test_fused_deep_wide(deep_rule, g_div, dim, mixed):
 
 
 class _Counted:
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
+    """``_C.emb_bwd_sparse``, counting calls by (deep rule, wide rule)."""
 
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
+    def __init__(self, fn):
+        self.fn, self.calls = fn, collections.Counter()
+
+    def __call__(self, deep, wide, *args):
+        self.calls[(deep and deep[0], wide and wide[0])] += 1
+        return self.fn(deep, wide, *args)
 
 
 @pytest.mark.parametrize("sharded", [False, True])
@@ -222,11 +226,8 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
                         wide_sparse_optimizer="ftrl", sparse_l1=l1,
                         sparse_l2=l2, wide_sparse_lr=WIDE_LR,
                         sparse_initial_accumulator=0.1).cuda()
-    counted = {name: _Counted(getattr(ops._C, name))
-               for name in ("emb_bwd_adagrad", "emb_bwd_ftrl_wide",
-                            "emb_bwd_adagrad_ftrl_fused_wide")}
-    for name, c in counted.items():
-        monkeypatch.setattr(ops._C, name, c)
+    counted = _Counted(ops._C.emb_bwd_sparse)
+    monkeypatch.setattr(ops._C, "emb_bwd_sparse", counted)
     if sharded:
         e = model.embeddings
         params = (e.weight, e.state_sum, e.wide_weight, e.wide_ftrl_accum,
@@ -252,16 +253,20 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
         for got, want in zip(params, (dt, ds, wt, wn, wz)):
             assert _close(got.detach(), want), step
     if sharded:
-        assert counted["emb_bwd_adagrad_ftrl_fused_wide"].calls == 2
-        assert counted["emb_bwd_adagrad"].calls == 0
+        assert counted.calls == {("adagrad", "ftrl"): 2}
     else:
-        assert counted["emb_bwd_adagrad"].calls == 2
-        assert counted["emb_bwd_ftrl_wide"].calls == 2
+        assert counted.calls == {("adagrad", None): 2, (None, "ftrl"): 2}
     big = [(name, buf) for name, buf in model.named_buffers()
            if "state_sum" in name or "ftrl" in name or "_adagrad" in name]
     assert len(big) >= 6
     for name, buf in big:
         assert buf.is_cuda and getattr(buf, "_miyarn_sharded", False), name
+
+
+def _ftrl_side(table, accum, linear, acc, grad, lr=LR, l1=0.0, l2=0.0):
+    """An FTRL side as ``_C.emb_bwd_sparse`` takes it (``grad=None``: pass
+    2 alone)."""
+    return ("ftrl", table, [accum, linear], acc, grad, lr, 1e-10, l1, l2)
 
 
 def test_bad_inputs_raise_before_any_launch():
@@ -275,8 +280,9 @@ def test_bad_inputs_raise_before_any_launch():
 
     def call(table=table, accum=accum, linear=linear, acc=ws.acc,
              stamp=ws.stamp, ids=ids, grad=grad, lr=LR, l1=0.0, l2=0.0):
-        ops._C.emb_bwd_ftrl(table, accum, linear, acc, stamp, ids, grad, 1,
-                            lr, l1, l2, 1.0)
+        ops._C.emb_bwd_sparse(
+            _ftrl_side(table, accum, linear, acc, grad, lr, l1, l2), None,
+            stamp, ids, 1, 1.0)
 
     bad = [
         dict(grad=grad.half()),                       # dtype
@@ -311,24 +317,29 @@ def test_bad_inputs_raise_before_any_launch():
     bf16_gw = torch.ones(10, dtype=torch.bfloat16).cuda()
     gw = torch.ones(10).cuda()
     with pytest.raises(RuntimeError):  # gw dtype differs from grad's
-        ops._C.emb_bwd_adagrad_ftrl_fused_wide(
-            table, accum, wws.acc, wide, wn, wz, wws.wide_acc, wws.stamp,
-            ids, grad, bf16_gw, 1, LR, 1e-10, LR, 0.0, 0.0, 1.0)
+        ops._C.emb_bwd_sparse(
+            ("adagrad", table, [accum], wws.acc, grad, LR, 1e-10, 0.0, 0.0),
+            _ftrl_side(wide, wn, wz, wws.wide_acc, bf16_gw),
+            wws.stamp, ids, 1, 1.0)
     with pytest.raises(RuntimeError):  # wide linear is deep-shaped
-        ops._C.emb_bwd_ftrl_fused_wide(
-            table, accum, linear, wws.acc, wide, wn, linear, wws.wide_acc,
-            wws.stamp, ids, grad, gw, 1, LR, LR, 0.0, 0.0, 1.0)
+        ops._C.emb_bwd_sparse(
+            _ftrl_side(table, accum, linear, wws.acc, grad),
+            _ftrl_side(wide, wn, linear, wws.wide_acc, gw),
+            wws.stamp, ids, 1, 1.0)
     with pytest.raises(RuntimeError):  # negative l1 on the fused entry
-        ops._C.emb_bwd_ftrl_fused_wide(
-            table, accum, linear, wws.acc, wide, wn, wz, wws.wide_acc,
-            wws.stamp, ids, grad, gw, 1, LR, LR, -1.0, 0.0, 1.0)
+        ops._C.emb_bwd_sparse(
+            _ftrl_side(table, accum, linear, wws.acc, grad, l1=-1.0),
+            _ftrl_side(wide, wn, wz, wws.wide_acc, gw, l1=-1.0),
+            wws.stamp, ids, 1, 1.0)
     with pytest.raises(RuntimeError):  # 40 ids, 7 examples
-        ops._C.emb_bwd_ftrl_wide(
-            wide, wn, wz, wws.wide_acc, wws.stamp, ids,
-            torch.ones(7).cuda(), 1, LR, 0.0, 0.0, 1.0)
+        ops._C.emb_bwd_sparse(
+            None, _ftrl_side(wide, wn, wz, wws.wide_acc,
+                             torch.ones(7).cuda()),
+            wws.stamp, ids, 1, 1.0)
     with pytest.raises(RuntimeError):  # pass 2 alone checks too
-        ops._C.sparse_ftrl_apply(table, accum, linear[:49].contiguous(),
-                                 ws.acc, ws.stamp, ids, 1, LR, 0.0, 0.0)
+        ops._C.emb_bwd_sparse(
+            _ftrl_side(table, accum, linear[:49].contiguous(), ws.acc, None),
+            None, ws.stamp, ids, 1, 1.0)
     torch.cuda.synchronize()
     assert torch.equal(table, t0)
     assert torch.equal(accum, torch.ones_like(accum))

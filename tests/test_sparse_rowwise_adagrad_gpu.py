@@ -12,6 +12,8 @@ contraction, the class the element-wise sparse Adagrad tests hold to
 ``torch.allclose(atol=1e-5)`` against the CPU op; the same call is used
 for table and state here."""
 
+import collections
+
 import pytest
 import torch
 
@@ -249,12 +251,14 @@ def test_two_gpu_runs_agree_bit_for_bit(dim):
 
 
 class _Counted:
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
+    """``_C.emb_bwd_sparse``, counting calls by (deep rule, wide rule)."""
 
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
+    def __init__(self, fn):
+        self.fn, self.calls = fn, collections.Counter()
+
+    def __call__(self, deep, wide, *args):
+        self.calls[(deep and deep[0], wide and wide[0])] += 1
+        return self.fn(deep, wide, *args)
 
 
 @pytest.mark.parametrize("wide_rule", ["adagrad", "ftrl"])
@@ -272,14 +276,8 @@ def test_model_update_runs_the_hip_kernels(sharded, wide_rule, monkeypatch):
                         wide_sparse_lr=WIDE_LR if ftrl else None,
                         sparse_initial_accumulator=0.1).cuda()
     assert model.wide_sparse_optimizer == wide_rule
-    fused = ("emb_bwd_rowwise_adagrad_ftrl_fused_wide" if ftrl
-             else "emb_bwd_rowwise_adagrad_fused_wide")
-    wide_single = "emb_bwd_ftrl_wide" if ftrl else "emb_bwd_adagrad_wide"
-    counted = {name: _Counted(getattr(ops._C, name))
-               for name in ("emb_bwd_rowwise_adagrad", wide_single, fused,
-                            "emb_bwd_adagrad")}
-    for name, c in counted.items():
-        monkeypatch.setattr(ops._C, name, c)
+    counted = _Counted(ops._C.emb_bwd_sparse)
+    monkeypatch.setattr(ops._C, "emb_bwd_sparse", counted)
     wide_names = ["ftrl_accum", "ftrl_linear"] if ftrl else ["state_sum"]
     if sharded:
         e = model.embeddings
@@ -312,20 +310,23 @@ def test_model_update_runs_the_hip_kernels(sharded, wide_rule, monkeypatch):
             ops.emb_bwd_adagrad_wide(*want[2:], w_ids, w_grad, lr=LR)
         for got, ref in zip(params, want):
             assert _close(got.detach(), ref), step
-    if sharded:
-        assert counted[fused].calls == 2
-        assert counted["emb_bwd_rowwise_adagrad"].calls == 0
-        assert counted[wide_single].calls == 0
-    else:
-        assert counted["emb_bwd_rowwise_adagrad"].calls == 2
-        assert counted[wide_single].calls == 2
-        assert counted[fused].calls == 0
-    assert counted["emb_bwd_adagrad"].calls == 0
+    if sharded:  # the fused pair alone: no single-table call
+        assert counted.calls == {("rowwise_adagrad", wide_rule): 2}
+    else:  # the two singles alone: no pair, no element-wise deep Adagrad
+        assert counted.calls == {("rowwise_adagrad", None): 2,
+                                 (None, wide_rule): 2}
     big = [(name, buf) for name, buf in model.named_buffers()
            if "state_sum" in name or "ftrl" in name or "_adagrad" in name]
     assert len(big) >= 5
     for name, buf in big:
         assert buf.is_cuda and getattr(buf, "_miyarn_sharded", False), name
+
+
+def _side(table, state_row, acc, grad):
+    """A row-wise Adagrad side as ``_C.emb_bwd_sparse`` takes it
+    (``grad=None``: pass 2 alone)."""
+    return ("rowwise_adagrad", table, [state_row], acc, grad, LR, 1e-10,
+            0.0, 0.0)
 
 
 def test_bad_inputs_raise_before_any_launch():
@@ -338,15 +339,15 @@ def test_bad_inputs_raise_before_any_launch():
 
     def call(table=table, state=state, acc=ws.acc, stamp=ws.stamp, ids=ids,
              grad=grad):
-        ops._C.emb_bwd_rowwise_adagrad(table, state, acc, stamp, ids, grad,
-                                       1, LR, 1e-10, 1.0)
+        ops._C.emb_bwd_sparse(_side(table, state, acc, grad), None, stamp,
+                              ids, 1, 1.0)
 
     def apply(**kw):  # pass 2 alone takes the same checks
         kw = dict(dict(table=table, state=state, acc=ws.acc,
                        stamp=ws.stamp, ids=ids), **kw)
-        ops._C.sparse_rowwise_adagrad_apply(
-            kw["table"], kw["state"], kw["acc"], kw["stamp"], kw["ids"], 1,
-            LR, 1e-10)
+        ops._C.emb_bwd_sparse(
+            _side(kw["table"], kw["state"], kw["acc"], None), None,
+            kw["stamp"], kw["ids"], 1, 1.0)
 
     bad_state = [
         dict(state=torch.zeros(50, 16).cuda()),       # the table's shape
@@ -377,15 +378,18 @@ def test_bad_inputs_raise_before_any_launch():
     gw = torch.ones(10).cuda()
 
     def pair(state=state, gw=gw, wide_state=torch.zeros_like(wide)):
-        ops._C.emb_bwd_rowwise_adagrad_fused_wide(
-            table, state, wws.acc, wide, wide_state, wws.wide_acc,
-            wws.stamp, ids, grad, gw, 1, LR, 1e-10, 1.0)
+        ops._C.emb_bwd_sparse(
+            _side(table, state, wws.acc, grad),
+            ("adagrad", wide, [wide_state], wws.wide_acc, gw, LR, 1e-10,
+             0.0, 0.0),
+            wws.stamp, ids, 1, 1.0)
 
     def pair_ftrl(state=state, gw=gw, lr=WIDE_LR):
-        ops._C.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-            table, state, wws.acc, wide, torch.zeros_like(wide),
-            torch.zeros_like(wide), wws.wide_acc, wws.stamp, ids, grad, gw,
-            1, LR, 1e-10, lr, 0.0, 0.0, 1.0)
+        ops._C.emb_bwd_sparse(
+            _side(table, state, wws.acc, grad),
+            ("ftrl", wide, [torch.zeros_like(wide), torch.zeros_like(wide)],
+             wws.wide_acc, gw, lr, 1e-10, 0.0, 0.0),
+            wws.stamp, ids, 1, 1.0)
 
     for fn in (pair, pair_ftrl):
         for kw in bad_state:
@@ -402,10 +406,11 @@ def test_bad_inputs_raise_before_any_launch():
     with pytest.raises(RuntimeError):  # the pair kernel does not take dim 12
         t12 = torch.zeros(50, 12).cuda()
         w12 = ops.SparseWorkspace(t12, wide)
-        ops._C.emb_bwd_rowwise_adagrad_fused_wide(
-            t12, state, w12.acc, wide, torch.zeros_like(wide), w12.wide_acc,
-            w12.stamp, ids, torch.ones(40, 12).cuda(), gw, 1, LR, 1e-10,
-            1.0)
+        ops._C.emb_bwd_sparse(
+            _side(t12, state, w12.acc, torch.ones(40, 12).cuda()),
+            ("adagrad", wide, [torch.zeros_like(wide)], w12.wide_acc, gw,
+             LR, 1e-10, 0.0, 0.0),
+            w12.stamp, ids, 1, 1.0)
     torch.cuda.synchronize()
     assert torch.equal(table, t0)
     assert not state.any() and not ws.acc.any() and not ws.stamp.any()

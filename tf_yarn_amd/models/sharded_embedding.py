@@ -557,59 +557,15 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         return (self.sparse_optimizer, self.wide_sparse_optimizer) != \
             ("sgd", "sgd")
 
-    # rule pairs (deep, wide) that have a fused deep+wide entry point
-    _FUSED_PAIRS = (("adagrad", "adagrad"), ("adagrad", "ftrl"),
-                    ("ftrl", "ftrl"), ("rowwise_adagrad", "adagrad"),
-                    ("rowwise_adagrad", "ftrl"))
-
-    def _apply_fused_pair(self, flat_ids, grad2d, gw, lr: float,
-                          wide_lr: float, scale: float, ws) -> None:
-        pair = (self.sparse_optimizer, self.wide_sparse_optimizer)
-        deep, wide = self.weight.data, self.wide_weight.data
-        if pair == ("adagrad", "adagrad") and wide_lr == lr:
-            ops.emb_bwd_adagrad_fused_wide(
-                deep, self.state_sum, wide, self.wide_state_sum, flat_ids,
-                grad2d, gw, lr=lr, eps=self.sparse_eps, scale=scale,
-                workspace=ws)
-        elif pair == ("adagrad", "ftrl"):
-            ops.emb_bwd_adagrad_ftrl_fused_wide(
-                deep, self.state_sum, wide, self.wide_ftrl_accum,
-                self.wide_ftrl_linear, flat_ids, grad2d, gw, lr=lr,
-                eps=self.sparse_eps, wide_lr=wide_lr, l1=self.sparse_l1,
-                l2=self.sparse_l2, scale=scale, workspace=ws)
-        elif pair == ("ftrl", "ftrl"):
-            ops.emb_bwd_ftrl_fused_wide(
-                deep, self.ftrl_accum, self.ftrl_linear, wide,
-                self.wide_ftrl_accum, self.wide_ftrl_linear, flat_ids,
-                grad2d, gw, lr=lr, wide_lr=wide_lr, l1=self.sparse_l1,
-                l2=self.sparse_l2, scale=scale, workspace=ws)
-        elif pair == ("rowwise_adagrad", "adagrad") and wide_lr == lr:
-            ops.emb_bwd_rowwise_adagrad_fused_wide(
-                deep, self.state_sum_row, wide, self.wide_state_sum,
-                flat_ids, grad2d, gw, lr=lr, eps=self.sparse_eps,
-                scale=scale, workspace=ws)
-        elif pair == ("rowwise_adagrad", "ftrl"):
-            ops.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-                deep, self.state_sum_row, wide, self.wide_ftrl_accum,
-                self.wide_ftrl_linear, flat_ids, grad2d, gw, lr=lr,
-                eps=self.sparse_eps, wide_lr=wide_lr, l1=self.sparse_l1,
-                l2=self.sparse_l2, scale=scale, workspace=ws)
-        else:  # an Adagrad pair at two rates: the fused kernels have one lr
-            self._sparse_apply_one(self.sparse_optimizer, "", deep,
-                                   flat_ids, grad2d, lr, scale, ws,
-                                   wide=False)
-            self._sparse_apply_one(self.wide_sparse_optimizer, "wide_",
-                                   wide, flat_ids, gw, wide_lr, scale,
-                                   ws.wide_view(), wide=True)
-
     def _apply_pending_stateful(self, lr: float) -> None:
         """Owner-local update when at least one table has a stateful rule
-        (Adagrad, FTRL).  Deep and wide sink entries that share their
-        flat ids take the fused deep+wide entry of their rule pair (ids
-        read once per pass, one claim per row for both tables), as the
-        SGD path does; everything else, pairs with SGD on one side
-        included, takes single-table calls.  The binned scatter is never
-        used here."""
+        (Adagrad, FTRL, row-wise Adagrad).  Deep and wide sink entries that
+        share their flat ids go to ``ops.emb_bwd_sparse`` as one pair when
+        both rules are stateful: it runs the pair's fused deep+wide kernel
+        where there is one (ids read once per pass, one claim per row for
+        both tables) and the two single-table updates otherwise.  An SGD
+        side is applied here, next to a single-table stateful call.  The
+        binned scatter is never used here."""
         scale = 1.0 / self.world
         deep_rule, wide_rule = (self.sparse_optimizer,
                                 self.wide_sparse_optimizer)
@@ -622,18 +578,22 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         else:
             deep_ws = self._adagrad_workspace(deep, wide)
             wide_ws = deep_ws.wide_view()
-        fusable = (deep_rule, wide_rule) in self._FUSED_PAIRS
+        both_stateful = "sgd" not in (deep_rule, wide_rule)
         wide_by_ids = {gw_ids.data_ptr(): (i, gw)
                        for i, (gw_ids, gw) in enumerate(self._wide_sink)}
-        fused_wide_done = set()
+        paired_wide_done = set()
         for flat_ids, grad in self._deep_sink:
             grad2d = grad.reshape(flat_ids.numel(), self.dim)
             mate = wide_by_ids.get(flat_ids.data_ptr())
-            if (fusable and mate is not None
-                    and mate[0] not in fused_wide_done):
-                self._apply_fused_pair(flat_ids, grad2d, mate[1], lr,
-                                       wide_lr, scale, deep_ws)
-                fused_wide_done.add(mate[0])
+            if (both_stateful and mate is not None
+                    and mate[0] not in paired_wide_done):
+                ops.emb_bwd_sparse(
+                    flat_ids,
+                    deep=self._sparse_side(deep_rule, "", deep, grad2d, lr),
+                    wide=self._sparse_side(wide_rule, "wide_", wide,
+                                           mate[1], wide_lr),
+                    scale=scale, workspace=deep_ws)
+                paired_wide_done.add(mate[0])
             elif deep_rule == "sgd":
                 ops.emb_bwd_sgd(deep, flat_ids, grad2d, lr=lr, scale=scale)
             else:
@@ -642,7 +602,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                                        wide=False)
         self._deep_sink.clear()
         for i, (flat_ids, gw) in enumerate(self._wide_sink):
-            if i in fused_wide_done:
+            if i in paired_wide_done:
                 continue
             if wide_rule == "sgd":
                 fan = self.F if self.world == 1 else self.f_own

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -58,6 +58,22 @@ def _check_sparse_rule(name: str, value: str, dim: int = 1) -> str:
         raise ValueError(
             f"{name} must be one of {allowed}, got {value!r}")
     return value
+
+
+class _State(NamedTuple):
+    """One persistent state buffer of a stateful sparse rule."""
+    name: str  # under the table's prefix ("" or "wide_")
+    from_init: bool = True  # starts at sparse_initial_accumulator, else at 0
+    per_row: bool = False  # shape [rows] instead of the table's
+
+
+# stateful rule -> its state buffers, in the order the ops take them.  A new
+# rule is one entry here.
+_RULE_STATES = {
+    "adagrad": (_State("state_sum"),),
+    "rowwise_adagrad": (_State("state_sum_row", per_row=True),),
+    "ftrl": (_State("ftrl_accum"), _State("ftrl_linear", from_init=False)),
+}
 
 
 def _default_wide_rule(sparse_optimizer: str) -> str:
@@ -125,24 +141,18 @@ class SparseOptimizerMixin:
         for prefix, (table, rule) in tables.items():
             if rule == "sgd":
                 continue
-            like = table.detach()
-            if rule == "adagrad":
-                fills = {prefix + "state_sum": init}
-            elif rule == "rowwise_adagrad":
-                fills = {prefix + "state_sum_row": init}
-                like = like[:, 0]  # one state value per row: [rows]
-            else:
-                fills = {prefix + "ftrl_accum": init,
-                         prefix + "ftrl_linear": 0.0}
-            for name, value in fills.items():
+            names = [prefix + st.name for st in _RULE_STATES[rule]]
+            for st in _RULE_STATES[rule]:
+                like = table.detach()[:, 0] if st.per_row else table.detach()
                 self.register_buffer(
-                    name, torch.full(like.shape, value, dtype=like.dtype,
-                                     device=like.device),
+                    prefix + st.name,
+                    torch.full(like.shape, init if st.from_init else 0.0,
+                               dtype=like.dtype, device=like.device),
                     persistent=True)
             acc = ("_adagrad_acc" if n_stateful == 0
                    else f"_adagrad_acc{n_stateful}")
             self.register_buffer(acc, None, persistent=False)
-            self._sparse_buffer_names += list(fills) + [acc]
+            self._sparse_buffer_names += names + [acc]
             n_stateful += 1
         if n_stateful == 0:
             return
@@ -150,29 +160,24 @@ class SparseOptimizerMixin:
         self._sparse_buffer_names.append("_adagrad_stamp")
         self._flag_sparse_buffers()
 
+    def _sparse_side(self, rule: str, prefix: str, table: torch.Tensor,
+                     grad: torch.Tensor, lr: float) -> "ops.SparseSide":
+        """A table's side of a stateful update (``rule`` is not "sgd") with
+        this module's state buffers ``<prefix>...`` and scalars."""
+        return ops.SparseSide(
+            rule, table,
+            tuple(getattr(self, prefix + st.name)
+                  for st in _RULE_STATES[rule]),
+            grad, lr, self.sparse_eps, self.sparse_l1, self.sparse_l2)
+
     def _sparse_apply_one(self, rule: str, prefix: str,
                           table: torch.Tensor, ids: torch.Tensor,
                           grad: torch.Tensor, lr: float, scale: float,
                           workspace, wide: bool) -> None:
-        """One single-table stateful update (``rule`` is not "sgd") with
-        this module's state buffers ``<prefix>...``."""
-        if rule == "rowwise_adagrad":  # never the wide table's rule
-            ops.emb_bwd_rowwise_adagrad(
-                table, getattr(self, prefix + "state_sum_row"), ids, grad,
-                lr=lr, eps=self.sparse_eps, scale=scale,
-                workspace=workspace)
-            return
-        if rule == "adagrad":
-            fn = ops.emb_bwd_adagrad_wide if wide else ops.emb_bwd_adagrad
-            fn(table, getattr(self, prefix + "state_sum"), ids, grad,
-               lr=lr, eps=self.sparse_eps, scale=scale,
-               workspace=workspace)
-            return
-        fn = ops.emb_bwd_ftrl_wide if wide else ops.emb_bwd_ftrl
-        fn(table, getattr(self, prefix + "ftrl_accum"),
-           getattr(self, prefix + "ftrl_linear"), ids, grad, lr=lr,
-           l1=self.sparse_l1, l2=self.sparse_l2, scale=scale,
-           workspace=workspace)
+        """One single-table stateful update."""
+        side = self._sparse_side(rule, prefix, table, grad, lr)
+        ops.emb_bwd_sparse(ids, **{"wide" if wide else "deep": side},
+                           scale=scale, workspace=workspace)
 
     def _flag_sparse_buffers(self) -> None:
         for name in getattr(self, "_sparse_buffer_names", ()):
@@ -200,12 +205,12 @@ class SparseOptimizerMixin:
 
     def _adagrad_workspace(self, table: torch.Tensor,
                            wide_table: Optional[torch.Tensor] = None
-                           ) -> "ops.SparseAdagradWorkspace":
+                           ) -> "ops.SparseWorkspace":
         """The module's workspace, bound to its non-persistent buffers
         (allocated on first use, re-bound after a device move)."""
         ws = self._sparse_ws
         if ws is None:
-            ws = ops.SparseAdagradWorkspace(table, wide_table)
+            ws = ops.SparseWorkspace(table, wide_table)
             self._sparse_ws = ws
             self._adagrad_acc = ws.acc
             if wide_table is not None:

@@ -9,8 +9,9 @@ implementations so every numerics test has a CPU baseline.
 
 from __future__ import annotations
 
+import functools
 import logging
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -346,11 +347,13 @@ def emb_bwd_dense(grad_table: torch.Tensor, ids: torch.Tensor,
                           alpha=scale)
 
 
-# ---- sparse Adagrad --------------------------------------------------------
+# ---- stateful sparse updates (Adagrad, FTRL, row-wise Adagrad) -------------
 
-class SparseAdagradWorkspace:
-    """Device scratch of the accumulate-then-claim sparse Adagrad kernels
-    for one table (optionally with its ``[rows, 1]`` wide companion).
+class SparseWorkspace:
+    """Device scratch of the accumulate-then-claim sparse kernels for one
+    table (optionally with its ``[rows, 1]`` wide companion).  It holds no
+    rule state, so one instance, and so one stamp, serves a deep table and
+    its wide companion whatever their rules.
 
     ``acc`` (and ``wide_acc``): fp32, shaped like the table, ALL-ZERO
     between calls — pass 1 scatter-adds into it and pass 2 zeroes every
@@ -384,8 +387,11 @@ class SparseAdagradWorkspace:
         return _WideWorkspaceView(self)
 
 
+SparseAdagradWorkspace = SparseWorkspace  # the name from before FTRL
+
+
 class _WideWorkspaceView:
-    def __init__(self, ws: SparseAdagradWorkspace):
+    def __init__(self, ws: SparseWorkspace):
         self._ws = ws
 
     @property
@@ -417,110 +423,6 @@ def _adagrad_rows_ref(table: torch.Tensor, state_sum: torch.Tensor,
     table.index_copy_(0, uniq, w)
 
 
-def emb_bwd_adagrad(table: torch.Tensor, state_sum: torch.Tensor,
-                    ids: torch.Tensor, grad: torch.Tensor, *, lr: float,
-                    eps: float = 1e-10, scale: float = 1.0,
-                    workspace: Optional[SparseAdagradWorkspace] = None
-                    ) -> None:
-    """Sparse Adagrad on the rows named by ``ids``.  For each unique id u:
-    ``G = scale * sum(grad[i] for ids[i] == u)``; ``state_sum[u] += G*G``;
-    ``table[u] -= lr * G / (sqrt(state_sum[u]) + eps)``.  Rows not in
-    ``ids`` are neither read nor written.  ``grad`` fp32 or bf16, table
-    and state fp32, any ``dim >= 1``.
-
-    GPU: atomic scatter into ``workspace.acc`` (the existing
-    ``emb_bwd_dense`` kernel), then the claim kernel updates each touched
-    row exactly once (``csrc/sparse_adagrad.hip``).  Pass a persistent
-    :class:`SparseAdagradWorkspace`; without one a table-sized scratch is
-    allocated for the call."""
-    flat = ids.reshape(-1)
-    if _on_gpu(table, state_sum, ids, grad):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseAdagradWorkspace(table)
-        _C.emb_bwd_adagrad(table, state_sum, ws.acc, ws.stamp,
-                           flat.contiguous(), grad.contiguous(),
-                           ws.next_epoch(), lr, eps, scale)
-        return
-    _adagrad_rows_ref(table, state_sum, flat,
-                      grad.reshape(flat.numel(), -1), lr, eps, scale)
-
-
-def emb_bwd_adagrad_wide(table: torch.Tensor, state_sum: torch.Tensor,
-                         ids: torch.Tensor, gw: torch.Tensor, *, lr: float,
-                         eps: float = 1e-10, scale: float = 1.0,
-                         workspace: Optional[SparseAdagradWorkspace] = None
-                         ) -> None:
-    """:func:`emb_bwd_adagrad` for the ``[rows, 1]`` wide table: the
-    gradient of flat update i is the per-example ``gw[i // g_div]``,
-    ``g_div = ids.numel() // gw.numel()`` (layout of
-    :func:`emb_scatter_sum`)."""
-    flat = ids.reshape(-1)
-    if _on_gpu(table, state_sum, ids, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseAdagradWorkspace(table)
-        _C.emb_bwd_adagrad_wide(table, state_sum, ws.acc, ws.stamp,
-                                flat.contiguous(),
-                                gw.reshape(-1).contiguous(),
-                                ws.next_epoch(), lr, eps, scale)
-        return
-    if flat.numel() == 0:
-        return
-    g_div = flat.numel() // gw.numel()
-    rows = gw.float().reshape(-1, 1).expand(-1, g_div).reshape(-1, 1)
-    _adagrad_rows_ref(table.reshape(-1, 1), state_sum.reshape(-1, 1), flat,
-                      rows, lr, eps, scale)
-
-
-def emb_bwd_adagrad_fused_wide(table: torch.Tensor, state_sum: torch.Tensor,
-                               wide_table: torch.Tensor,
-                               wide_state_sum: torch.Tensor,
-                               ids: torch.Tensor, grad: torch.Tensor,
-                               gw: torch.Tensor, *, lr: float,
-                               eps: float = 1e-10, scale: float = 1.0,
-                               workspace: Optional[
-                                   SparseAdagradWorkspace] = None) -> None:
-    """Sparse Adagrad on BOTH CTR tables from the shared flat ids (the
-    Adagrad mirror of :func:`emb_bwd_sgd_fused_wide`): the ids are read
-    once per pass and the winner of a deep row also applies the wide
-    scalar.  ``workspace`` must have been built with ``wide_table``.
-    Shapes the fused kernels do not cover (``dim/4`` not a power of two
-    <= 64, mixed grad dtypes) take the two single-table ops, sharing the
-    workspace's stamp across two epochs."""
-    if _on_gpu(table, ids, grad, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseAdagradWorkspace(table, wide_table)
-        dvec, rem = divmod(table.shape[1], 4)
-        if (rem == 0 and 1 <= dvec <= 64 and dvec & (dvec - 1) == 0
-                and grad.dtype == gw.dtype):
-            _C.emb_bwd_adagrad_fused_wide(
-                table, state_sum, ws.acc, wide_table, wide_state_sum,
-                ws.wide_acc, ws.stamp, ids.reshape(-1).contiguous(),
-                grad.contiguous(), gw.reshape(-1).contiguous(),
-                ws.next_epoch(), lr, eps, scale)
-            return
-        emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
-                        scale=scale, workspace=ws)
-        emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
-                             eps=eps, scale=scale,
-                             workspace=ws.wide_view())
-        return
-    emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
-                    scale=scale)
-    emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
-                         eps=eps, scale=scale)
-
-
-# ---- sparse FTRL -----------------------------------------------------------
-
-# The workspace holds no rule state (accumulator + stamp + epoch): one
-# instance, and so one stamp, serves a deep Adagrad table and its wide
-# FTRL companion.
-SparseWorkspace = SparseAdagradWorkspace
-
-
 def _ftrl_rows_ref(table: torch.Tensor, accum: torch.Tensor,
                    linear: torch.Tensor, flat_ids: torch.Tensor,
                    rows: torch.Tensor, lr: float, l1: float, l2: float,
@@ -541,13 +443,190 @@ def _ftrl_rows_ref(table: torch.Tensor, accum: torch.Tensor,
     table.index_copy_(0, uniq, w)
 
 
-def _fused_pair_covers(table: torch.Tensor, grad: torch.Tensor,
-                       gw: torch.Tensor) -> bool:
-    """Shapes the fused deep+wide kernels take: ``dim/4`` a power of two
-    <= 64 and one gradient dtype."""
-    dvec, rem = divmod(table.shape[1], 4)
-    return (rem == 0 and 1 <= dvec <= 64 and dvec & (dvec - 1) == 0
-            and grad.dtype == gw.dtype)
+def _rowwise_adagrad_rows_ref(table: torch.Tensor, state_row: torch.Tensor,
+                              flat_ids: torch.Tensor, rows: torch.Tensor,
+                              lr: float, eps: float, scale: float) -> None:
+    """Reference: coalesce duplicate ids, then one row-wise Adagrad step
+    on the unique rows.  The mean of squares is a true division by ``dim``
+    (tensor / tensor, never a multiply by a reciprocal)."""
+    uniq, inv = torch.unique(flat_ids, return_inverse=True)
+    dim = rows.shape[1]
+    g = torch.zeros(uniq.numel(), dim, dtype=torch.float32,
+                    device=rows.device)
+    g.index_add_(0, inv, rows.float())
+    g.mul_(scale)
+    ss = (g * g).sum(dim=1)
+    s = state_row.index_select(0, uniq) + ss / torch.full_like(ss, dim)
+    state_row.index_copy_(0, uniq, s)
+    w = table.index_select(0, uniq).addcdiv_(
+        g, s.sqrt().add_(eps).unsqueeze(1), value=-lr)
+    table.index_copy_(0, uniq, w)
+
+
+class SparseSide(NamedTuple):
+    """One table's side of a stateful sparse update: the rule (``"adagrad"``,
+    ``"ftrl"`` or ``"rowwise_adagrad"``), the table, the rule's state tensors
+    in the rule's order (``(state_sum,)``, ``(accum, linear)``,
+    ``(state_row,)``), the gradient (deep: ``[n, dim]``; wide: per example,
+    ``gw[i // g_div]``) and the rule's scalars; a rule ignores the scalars
+    it does not have."""
+    rule: str
+    table: torch.Tensor
+    states: Tuple[torch.Tensor, ...]
+    grad: torch.Tensor
+    lr: float
+    eps: float = 1e-10
+    l1: float = 0.0
+    l2: float = 0.0
+
+
+def _side_ref(side: SparseSide, flat: torch.Tensor, is_wide: bool,
+              scale: float) -> None:
+    """CPU reference of one side."""
+    if is_wide:
+        if flat.numel() == 0:
+            return
+        g_div = flat.numel() // side.grad.numel()
+        rows = side.grad.float().reshape(-1, 1).expand(-1, g_div) \
+            .reshape(-1, 1)
+        tensors = [t.reshape(-1, 1) for t in (side.table, *side.states)]
+    else:
+        rows = side.grad.reshape(flat.numel(), -1)
+        tensors = [side.table, *side.states]
+    if side.rule == "ftrl":
+        _ftrl_rows_ref(*tensors, flat, rows, side.lr, side.l1, side.l2,
+                       scale)
+    elif side.rule == "adagrad":
+        _adagrad_rows_ref(*tensors, flat, rows, side.lr, side.eps, scale)
+    else:
+        _rowwise_adagrad_rows_ref(side.table, side.states[0], flat, rows,
+                                  side.lr, side.eps, scale)
+
+
+def _side_arg(side: SparseSide, acc: torch.Tensor) -> tuple:
+    """A side as ``_C.emb_bwd_sparse`` takes it."""
+    rule, table, states, grad, lr, eps, l1, l2 = side
+    return (rule, table, states, acc, grad.contiguous(), lr, eps, l1, l2)
+
+
+@functools.lru_cache(maxsize=None)
+def _pair_fused_ok(deep_rule: str, wide_rule: str, dim: int) -> bool:
+    """``_C.sparse_pair_fused_ok``: the answer never changes, and the ops
+    ask once per update."""
+    return _C.sparse_pair_fused_ok(deep_rule, wide_rule, dim)
+
+
+def emb_bwd_sparse(ids: torch.Tensor, *, deep: Optional[SparseSide] = None,
+                   wide: Optional[SparseSide] = None, scale: float = 1.0,
+                   workspace=None) -> None:
+    """The stateful sparse update behind every ``emb_bwd_<rule>*`` op: on
+    the rows named by ``ids``, the ``deep`` table's side, the ``[rows, 1]``
+    ``wide`` table's side, or both from their shared flat ids.  For each
+    unique id u, ``G = scale * sum(grad[i] for ids[i] == u)``, then the
+    side's rule once per row; rows not in ``ids`` are neither read nor
+    written.
+
+    GPU: pass 1 scatter-adds into ``workspace.acc`` (/ ``wide_acc``), pass
+    2 claims each touched row once and applies the rule
+    (``csrc/sparse_adagrad.hip``).  A pair runs as ONE fused update (ids
+    read once per pass, the winner of a deep row also applies the wide
+    scalar) when ``_C.sparse_pair_fused_ok`` says there is a kernel for the
+    rule pair at this ``dim`` and both gradients have one dtype (an Adagrad
+    wide side also needs the deep side's ``lr``); otherwise the deep
+    side runs on the workspace and the wide side on its ``wide_view()``, on
+    the shared stamp across two epochs.  Pass a persistent
+    :class:`SparseWorkspace` (for a pair, built with the wide table);
+    without one a table-sized scratch is allocated for the call."""
+    sides = [s for s in (deep, wide) if s is not None]
+    for side in sides:
+        if side.rule == "ftrl":
+            _check_ftrl_args(side.lr, side.l1, side.l2)
+    flat = ids.reshape(-1)
+    if not (ids.is_cuda or any(t.is_cuda for s in sides
+                               for t in (s.table, s.grad, *s.states))):
+        for side in sides:
+            _side_ref(side, flat, side is wide, scale)
+        return
+    _require_ext()
+    ws = workspace
+    if ws is None:
+        ws = SparseWorkspace(sides[0].table,
+                             wide.table if len(sides) == 2 else None)
+    if len(sides) == 1:
+        side = _side_arg(sides[0], ws.acc)
+        _C.emb_bwd_sparse(side if deep is not None else None,
+                          side if wide is not None else None, ws.stamp,
+                          flat.contiguous(), ws.next_epoch(), scale)
+        return
+    # An Adagrad wide side under an Adagrad or row-wise Adagrad deep side is
+    # fused only at one shared lr: at two rates the pair has always taken
+    # the single ops.  The kernels carry per-side scalars; lifting this is a
+    # separate change.
+    if (_pair_fused_ok(deep.rule, wide.rule, deep.table.shape[1])
+            and deep.grad.dtype == wide.grad.dtype
+            and (wide.rule != "adagrad" or wide.lr == deep.lr)):
+        _C.emb_bwd_sparse(_side_arg(deep, ws.acc),
+                          _side_arg(wide, ws.wide_acc), ws.stamp,
+                          flat.contiguous(), ws.next_epoch(), scale)
+        return
+    emb_bwd_sparse(ids, deep=deep, scale=scale, workspace=ws)
+    emb_bwd_sparse(ids, wide=wide, scale=scale, workspace=ws.wide_view())
+
+
+def emb_bwd_adagrad(table: torch.Tensor, state_sum: torch.Tensor,
+                    ids: torch.Tensor, grad: torch.Tensor, *, lr: float,
+                    eps: float = 1e-10, scale: float = 1.0,
+                    workspace: Optional[SparseWorkspace] = None) -> None:
+    """Sparse Adagrad on the rows named by ``ids``.  For each unique id u:
+    ``G = scale * sum(grad[i] for ids[i] == u)``; ``state_sum[u] += G*G``;
+    ``table[u] -= lr * G / (sqrt(state_sum[u]) + eps)``.  Rows not in
+    ``ids`` are neither read nor written.  ``grad`` fp32 or bf16, table
+    and state fp32, any ``dim >= 1``.
+
+    GPU: atomic scatter into ``workspace.acc`` (the existing
+    ``emb_bwd_dense`` kernel), then the claim kernel updates each touched
+    row exactly once (``csrc/sparse_adagrad.hip``).  Pass a persistent
+    :class:`SparseWorkspace`; without one a table-sized scratch is
+    allocated for the call."""
+    emb_bwd_sparse(ids, deep=SparseSide("adagrad", table, (state_sum,),
+                                        grad, lr, eps),
+                   scale=scale, workspace=workspace)
+
+
+def emb_bwd_adagrad_wide(table: torch.Tensor, state_sum: torch.Tensor,
+                         ids: torch.Tensor, gw: torch.Tensor, *, lr: float,
+                         eps: float = 1e-10, scale: float = 1.0,
+                         workspace: Optional[SparseWorkspace] = None
+                         ) -> None:
+    """:func:`emb_bwd_adagrad` for the ``[rows, 1]`` wide table: the
+    gradient of flat update i is the per-example ``gw[i // g_div]``,
+    ``g_div = ids.numel() // gw.numel()`` (layout of
+    :func:`emb_scatter_sum`)."""
+    emb_bwd_sparse(ids, wide=SparseSide("adagrad", table, (state_sum,), gw,
+                                        lr, eps),
+                   scale=scale, workspace=workspace)
+
+
+def emb_bwd_adagrad_fused_wide(table: torch.Tensor, state_sum: torch.Tensor,
+                               wide_table: torch.Tensor,
+                               wide_state_sum: torch.Tensor,
+                               ids: torch.Tensor, grad: torch.Tensor,
+                               gw: torch.Tensor, *, lr: float,
+                               eps: float = 1e-10, scale: float = 1.0,
+                               workspace: Optional[SparseWorkspace] = None
+                               ) -> None:
+    """Sparse Adagrad on BOTH CTR tables from the shared flat ids (the
+    Adagrad mirror of :func:`emb_bwd_sgd_fused_wide`): the ids are read
+    once per pass and the winner of a deep row also applies the wide
+    scalar.  ``workspace`` must have been built with ``wide_table``.
+    Shapes the fused kernels do not cover (``dim/4`` not a power of two
+    <= 64, mixed grad dtypes) take the two single-table ops, sharing the
+    workspace's stamp across two epochs."""
+    emb_bwd_sparse(
+        ids, deep=SparseSide("adagrad", table, (state_sum,), grad, lr, eps),
+        wide=SparseSide("adagrad", wide_table, (wide_state_sum,), gw, lr,
+                        eps),
+        scale=scale, workspace=workspace)
 
 
 def emb_bwd_ftrl(table: torch.Tensor, accum: torch.Tensor,
@@ -572,17 +651,9 @@ def emb_bwd_ftrl(table: torch.Tensor, accum: torch.Tensor,
 
     GPU: the accumulate-then-claim kernels of :func:`emb_bwd_adagrad`
     with the FTRL rule (``csrc/sparse_adagrad.hip``)."""
-    _check_ftrl_args(lr, l1, l2)
-    flat = ids.reshape(-1)
-    if _on_gpu(table, accum, linear, ids, grad):
-        _require_ext()
-        ws = workspace if workspace is not None else SparseWorkspace(table)
-        _C.emb_bwd_ftrl(table, accum, linear, ws.acc, ws.stamp,
-                        flat.contiguous(), grad.contiguous(),
-                        ws.next_epoch(), lr, l1, l2, scale)
-        return
-    _ftrl_rows_ref(table, accum, linear, flat,
-                   grad.reshape(flat.numel(), -1), lr, l1, l2, scale)
+    emb_bwd_sparse(ids, deep=SparseSide("ftrl", table, (accum, linear),
+                                        grad, lr, l1=l1, l2=l2),
+                   scale=scale, workspace=workspace)
 
 
 def emb_bwd_ftrl_wide(table: torch.Tensor, accum: torch.Tensor,
@@ -592,21 +663,9 @@ def emb_bwd_ftrl_wide(table: torch.Tensor, accum: torch.Tensor,
                       workspace: Optional[SparseWorkspace] = None) -> None:
     """:func:`emb_bwd_ftrl` for the ``[rows, 1]`` wide table, with the
     ``gw[i // g_div]`` gradient layout of :func:`emb_bwd_adagrad_wide`."""
-    _check_ftrl_args(lr, l1, l2)
-    flat = ids.reshape(-1)
-    if _on_gpu(table, accum, linear, ids, gw):
-        _require_ext()
-        ws = workspace if workspace is not None else SparseWorkspace(table)
-        _C.emb_bwd_ftrl_wide(table, accum, linear, ws.acc, ws.stamp,
-                             flat.contiguous(), gw.reshape(-1).contiguous(),
-                             ws.next_epoch(), lr, l1, l2, scale)
-        return
-    if flat.numel() == 0:
-        return
-    g_div = flat.numel() // gw.numel()
-    rows = gw.float().reshape(-1, 1).expand(-1, g_div).reshape(-1, 1)
-    _ftrl_rows_ref(table.reshape(-1, 1), accum.reshape(-1, 1),
-                   linear.reshape(-1, 1), flat, rows, lr, l1, l2, scale)
+    emb_bwd_sparse(ids, wide=SparseSide("ftrl", table, (accum, linear), gw,
+                                        lr, l1=l1, l2=l2),
+                   scale=scale, workspace=workspace)
 
 
 def emb_bwd_adagrad_ftrl_fused_wide(
@@ -623,26 +682,11 @@ def emb_bwd_adagrad_ftrl_fused_wide(
     row for both.  ``workspace`` must have been built with ``wide_table``.
     Shapes the fused kernel does not cover take the two single-table ops
     on the shared stamp, as in :func:`emb_bwd_adagrad_fused_wide`."""
-    wide_lr = lr if wide_lr is None else wide_lr
-    _check_ftrl_args(wide_lr, l1, l2)
-    ws = None
-    if _on_gpu(table, ids, grad, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseWorkspace(table, wide_table)
-        if _fused_pair_covers(table, grad, gw):
-            _C.emb_bwd_adagrad_ftrl_fused_wide(
-                table, state_sum, ws.acc, wide_table, wide_accum,
-                wide_linear, ws.wide_acc, ws.stamp,
-                ids.reshape(-1).contiguous(), grad.contiguous(),
-                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, eps,
-                wide_lr, l1, l2, scale)
-            return
-    emb_bwd_adagrad(table, state_sum, ids, grad, lr=lr, eps=eps,
-                    scale=scale, workspace=ws)
-    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
-                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
-                      workspace=ws.wide_view() if ws is not None else None)
+    emb_bwd_sparse(
+        ids, deep=SparseSide("adagrad", table, (state_sum,), grad, lr, eps),
+        wide=SparseSide("ftrl", wide_table, (wide_accum, wide_linear), gw,
+                        lr if wide_lr is None else wide_lr, l1=l1, l2=l2),
+        scale=scale, workspace=workspace)
 
 
 def emb_bwd_ftrl_fused_wide(
@@ -655,49 +699,12 @@ def emb_bwd_ftrl_fused_wide(
     """Sparse FTRL on BOTH CTR tables from the shared flat ids (``l1`` and
     ``l2`` are shared; the wide table may run at its own ``wide_lr``).
     Fallback rule as in :func:`emb_bwd_adagrad_ftrl_fused_wide`."""
-    wide_lr = lr if wide_lr is None else wide_lr
-    _check_ftrl_args(lr, l1, l2)
-    _check_ftrl_args(wide_lr, l1, l2)
-    ws = None
-    if _on_gpu(table, ids, grad, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseWorkspace(table, wide_table)
-        if _fused_pair_covers(table, grad, gw):
-            _C.emb_bwd_ftrl_fused_wide(
-                table, accum, linear, ws.acc, wide_table, wide_accum,
-                wide_linear, ws.wide_acc, ws.stamp,
-                ids.reshape(-1).contiguous(), grad.contiguous(),
-                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, wide_lr,
-                l1, l2, scale)
-            return
-    emb_bwd_ftrl(table, accum, linear, ids, grad, lr=lr, l1=l1, l2=l2,
-                 scale=scale, workspace=ws)
-    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
-                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
-                      workspace=ws.wide_view() if ws is not None else None)
-
-
-# ---- row-wise sparse Adagrad -----------------------------------------------
-
-def _rowwise_adagrad_rows_ref(table: torch.Tensor, state_row: torch.Tensor,
-                              flat_ids: torch.Tensor, rows: torch.Tensor,
-                              lr: float, eps: float, scale: float) -> None:
-    """Reference: coalesce duplicate ids, then one row-wise Adagrad step
-    on the unique rows.  The mean of squares is a true division by ``dim``
-    (tensor / tensor, never a multiply by a reciprocal)."""
-    uniq, inv = torch.unique(flat_ids, return_inverse=True)
-    dim = rows.shape[1]
-    g = torch.zeros(uniq.numel(), dim, dtype=torch.float32,
-                    device=rows.device)
-    g.index_add_(0, inv, rows.float())
-    g.mul_(scale)
-    ss = (g * g).sum(dim=1)
-    s = state_row.index_select(0, uniq) + ss / torch.full_like(ss, dim)
-    state_row.index_copy_(0, uniq, s)
-    w = table.index_select(0, uniq).addcdiv_(
-        g, s.sqrt().add_(eps).unsqueeze(1), value=-lr)
-    table.index_copy_(0, uniq, w)
+    emb_bwd_sparse(
+        ids, deep=SparseSide("ftrl", table, (accum, linear), grad, lr,
+                             l1=l1, l2=l2),
+        wide=SparseSide("ftrl", wide_table, (wide_accum, wide_linear), gw,
+                        lr if wide_lr is None else wide_lr, l1=l1, l2=l2),
+        scale=scale, workspace=workspace)
 
 
 def emb_bwd_rowwise_adagrad(table: torch.Tensor, state_row: torch.Tensor,
@@ -722,17 +729,9 @@ def emb_bwd_rowwise_adagrad(table: torch.Tensor, state_row: torch.Tensor,
 
     GPU: pass 1 of :func:`emb_bwd_adagrad` into ``workspace.acc``, then
     the row-wise claim kernels of ``csrc/sparse_adagrad.hip``."""
-    flat = ids.reshape(-1)
-    if _on_gpu(table, state_row, ids, grad):
-        _require_ext()
-        ws = workspace if workspace is not None else SparseWorkspace(table)
-        _C.emb_bwd_rowwise_adagrad(table, state_row, ws.acc, ws.stamp,
-                                   flat.contiguous(), grad.contiguous(),
-                                   ws.next_epoch(), lr, eps, scale)
-        return
-    _rowwise_adagrad_rows_ref(table, state_row, flat,
-                              grad.reshape(flat.numel(), -1), lr, eps,
-                              scale)
+    emb_bwd_sparse(ids, deep=SparseSide("rowwise_adagrad", table,
+                                        (state_row,), grad, lr, eps),
+                   scale=scale, workspace=workspace)
 
 
 def emb_bwd_rowwise_adagrad_fused_wide(
@@ -745,26 +744,14 @@ def emb_bwd_rowwise_adagrad_fused_wide(
     wide scalars from the shared flat ids, at one ``lr`` and ``eps``: the
     winner of a deep row also applies the wide scalar.  ``workspace`` must
     have been built with ``wide_table``.  Shapes the fused kernel does not
-    cover (:func:`_fused_pair_covers`) take the two single-table ops on
-    the shared stamp, as in :func:`emb_bwd_adagrad_fused_wide`."""
-    ws = None
-    if _on_gpu(table, ids, grad, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseWorkspace(table, wide_table)
-        if _fused_pair_covers(table, grad, gw):
-            _C.emb_bwd_rowwise_adagrad_fused_wide(
-                table, state_row, ws.acc, wide_table, wide_state_sum,
-                ws.wide_acc, ws.stamp, ids.reshape(-1).contiguous(),
-                grad.contiguous(), gw.reshape(-1).contiguous(),
-                ws.next_epoch(), lr, eps, scale)
-            return
-    emb_bwd_rowwise_adagrad(table, state_row, ids, grad, lr=lr, eps=eps,
-                            scale=scale, workspace=ws)
-    emb_bwd_adagrad_wide(wide_table, wide_state_sum, ids, gw, lr=lr,
-                         eps=eps, scale=scale,
-                         workspace=ws.wide_view() if ws is not None
-                         else None)
+    cover take the two single-table ops on the shared stamp, as in
+    :func:`emb_bwd_adagrad_fused_wide`."""
+    emb_bwd_sparse(
+        ids, deep=SparseSide("rowwise_adagrad", table, (state_row,), grad,
+                             lr, eps),
+        wide=SparseSide("adagrad", wide_table, (wide_state_sum,), gw, lr,
+                        eps),
+        scale=scale, workspace=workspace)
 
 
 def emb_bwd_rowwise_adagrad_ftrl_fused_wide(
@@ -780,26 +767,12 @@ def emb_bwd_rowwise_adagrad_ftrl_fused_wide(
     (``wide_lr``, default ``lr``; ``l1``, ``l2``) on the wide scalars, one
     claim per row for both.  Fallback rule as in
     :func:`emb_bwd_rowwise_adagrad_fused_wide`."""
-    wide_lr = lr if wide_lr is None else wide_lr
-    _check_ftrl_args(wide_lr, l1, l2)
-    ws = None
-    if _on_gpu(table, ids, grad, gw):
-        _require_ext()
-        ws = workspace if workspace is not None \
-            else SparseWorkspace(table, wide_table)
-        if _fused_pair_covers(table, grad, gw):
-            _C.emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-                table, state_row, ws.acc, wide_table, wide_accum,
-                wide_linear, ws.wide_acc, ws.stamp,
-                ids.reshape(-1).contiguous(), grad.contiguous(),
-                gw.reshape(-1).contiguous(), ws.next_epoch(), lr, eps,
-                wide_lr, l1, l2, scale)
-            return
-    emb_bwd_rowwise_adagrad(table, state_row, ids, grad, lr=lr, eps=eps,
-                            scale=scale, workspace=ws)
-    emb_bwd_ftrl_wide(wide_table, wide_accum, wide_linear, ids, gw,
-                      lr=wide_lr, l1=l1, l2=l2, scale=scale,
-                      workspace=ws.wide_view() if ws is not None else None)
+    emb_bwd_sparse(
+        ids, deep=SparseSide("rowwise_adagrad", table, (state_row,), grad,
+                             lr, eps),
+        wide=SparseSide("ftrl", wide_table, (wide_accum, wide_linear), gw,
+                        lr if wide_lr is None else wide_lr, l1=l1, l2=l2),
+        scale=scale, workspace=workspace)
 
 
 # ---- elementwise -----------------------------------------------------------

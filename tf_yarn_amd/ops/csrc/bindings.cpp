@@ -1,5 +1,7 @@
 // Python bindings for the tf_yarn_amd MI355X kernel library.
 #include <torch/extension.h>
+#include <string>
+#include <tuple>
 #include <vector>
 
 // fused_optimizers.hip
@@ -61,104 +63,17 @@ void emb_scatter_sum(torch::Tensor table, torch::Tensor ids,
                      torch::Tensor grad, double alpha);
 
 // sparse_adagrad.hip
-void sparse_adagrad_apply(torch::Tensor table, torch::Tensor state_sum,
-                          torch::Tensor acc, torch::Tensor stamp,
-                          torch::Tensor ids, int64_t epoch, double lr,
-                          double eps);
-void sparse_adagrad_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    int64_t epoch, double lr, double eps);
-void emb_bwd_adagrad(torch::Tensor table, torch::Tensor state_sum,
-                     torch::Tensor acc, torch::Tensor stamp,
-                     torch::Tensor ids, torch::Tensor grad, int64_t epoch,
-                     double lr, double eps, double scale);
-void emb_bwd_adagrad_wide(torch::Tensor table, torch::Tensor state_sum,
-                          torch::Tensor acc, torch::Tensor stamp,
-                          torch::Tensor ids, torch::Tensor gw,
-                          int64_t epoch, double lr, double eps,
-                          double scale);
-void emb_bwd_adagrad_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
-    double eps, double scale);
-void sparse_ftrl_apply(torch::Tensor table, torch::Tensor accum,
-                       torch::Tensor linear, torch::Tensor acc,
-                       torch::Tensor stamp, torch::Tensor ids,
-                       int64_t epoch, double lr, double l1, double l2);
-void sparse_adagrad_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double eps,
-    double wide_lr, double l1, double l2);
-void sparse_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
-    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double wide_lr, double l1,
-    double l2);
-void emb_bwd_ftrl(torch::Tensor table, torch::Tensor accum,
-                  torch::Tensor linear, torch::Tensor acc,
-                  torch::Tensor stamp, torch::Tensor ids,
-                  torch::Tensor grad, int64_t epoch, double lr, double l1,
-                  double l2, double scale);
-void emb_bwd_ftrl_wide(torch::Tensor table, torch::Tensor accum,
-                       torch::Tensor linear, torch::Tensor acc,
-                       torch::Tensor stamp, torch::Tensor ids,
-                       torch::Tensor gw, int64_t epoch, double lr,
-                       double l1, double l2, double scale);
-void emb_bwd_adagrad_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double eps, double wide_lr, double l1, double l2,
-    double scale);
-void emb_bwd_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
-    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double wide_lr, double l1, double l2, double scale);
-void sparse_rowwise_adagrad_apply(torch::Tensor table,
-                                  torch::Tensor state_row,
-                                  torch::Tensor acc, torch::Tensor stamp,
-                                  torch::Tensor ids, int64_t epoch,
-                                  double lr, double eps);
-void sparse_rowwise_adagrad_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    int64_t epoch, double lr, double eps);
-void sparse_rowwise_adagrad_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double eps,
-    double wide_lr, double l1, double l2);
-void emb_bwd_rowwise_adagrad(torch::Tensor table, torch::Tensor state_row,
-                             torch::Tensor acc, torch::Tensor stamp,
-                             torch::Tensor ids, torch::Tensor grad,
-                             int64_t epoch, double lr, double eps,
-                             double scale);
-void emb_bwd_rowwise_adagrad_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
-    double eps, double scale);
-void emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double eps, double wide_lr, double l1, double l2,
-    double scale);
-
+// one table's side of a stateful sparse update: (rule name, table, state
+// tensors, accumulator, gradient or None, lr, eps, l1, l2)
+using SparseSide = std::tuple<std::string, torch::Tensor,
+                              std::vector<torch::Tensor>, torch::Tensor,
+                              c10::optional<torch::Tensor>, double, double,
+                              double, double>;
+void emb_bwd_sparse(c10::optional<SparseSide> deep,
+                    c10::optional<SparseSide> wide, torch::Tensor stamp,
+                    torch::Tensor ids, int64_t epoch, double scale);
+bool sparse_pair_fused_ok(const std::string& deep_rule,
+                          const std::string& wide_rule, int64_t dim);
 // binned_scatter.hip
 py::dict binned_layout();
 std::vector<torch::Tensor> binned_permutation(torch::Tensor ids,
@@ -249,52 +164,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("col_offset"));
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
-  m.def("sparse_adagrad_apply", &sparse_adagrad_apply,
-        "Sparse Adagrad pass 2: claim each touched row once, consume the "
-        "accumulator, update state + table");
-  m.def("sparse_adagrad_apply_fused_wide", &sparse_adagrad_apply_fused_wide,
-        "Sparse Adagrad pass 2 for the deep + wide pair (shared ids)");
-  m.def("emb_bwd_adagrad", &emb_bwd_adagrad,
-        "Sparse Adagrad: atomic accumulate + once-per-row claim/apply");
-  m.def("emb_bwd_adagrad_wide", &emb_bwd_adagrad_wide,
-        "Sparse Adagrad for the [rows, 1] wide table (gw[i / g_div])");
-  m.def("emb_bwd_adagrad_fused_wide", &emb_bwd_adagrad_fused_wide,
-        "Sparse Adagrad for the deep + wide pair (shared ids)");
-  m.def("sparse_ftrl_apply", &sparse_ftrl_apply,
-        "Sparse FTRL pass 2: claim each touched row once, consume the "
-        "accumulator, update accum + linear + table");
-  m.def("sparse_adagrad_ftrl_apply_fused_wide",
-        &sparse_adagrad_ftrl_apply_fused_wide,
-        "Pass 2 for a deep Adagrad + wide FTRL pair (shared ids)");
-  m.def("sparse_ftrl_apply_fused_wide", &sparse_ftrl_apply_fused_wide,
-        "Pass 2 for a deep FTRL + wide FTRL pair (shared ids)");
-  m.def("emb_bwd_ftrl", &emb_bwd_ftrl,
-        "Sparse FTRL-proximal: atomic accumulate + once-per-row "
-        "claim/apply");
-  m.def("emb_bwd_ftrl_wide", &emb_bwd_ftrl_wide,
-        "Sparse FTRL for the [rows, 1] wide table (gw[i / g_div])");
-  m.def("emb_bwd_adagrad_ftrl_fused_wide", &emb_bwd_adagrad_ftrl_fused_wide,
-        "Deep sparse Adagrad + wide sparse FTRL (shared ids)");
-  m.def("emb_bwd_ftrl_fused_wide", &emb_bwd_ftrl_fused_wide,
-        "Sparse FTRL for the deep + wide pair (shared ids)");
-  m.def("sparse_rowwise_adagrad_apply", &sparse_rowwise_adagrad_apply,
-        "Row-wise sparse Adagrad pass 2: claim each touched row once, "
-        "reduce its squares, update state_row[rows] + table");
-  m.def("sparse_rowwise_adagrad_apply_fused_wide",
-        &sparse_rowwise_adagrad_apply_fused_wide,
-        "Pass 2 for a deep row-wise Adagrad + wide Adagrad pair");
-  m.def("sparse_rowwise_adagrad_ftrl_apply_fused_wide",
-        &sparse_rowwise_adagrad_ftrl_apply_fused_wide,
-        "Pass 2 for a deep row-wise Adagrad + wide FTRL pair");
-  m.def("emb_bwd_rowwise_adagrad", &emb_bwd_rowwise_adagrad,
-        "Row-wise sparse Adagrad (one state value per row): atomic "
-        "accumulate + once-per-row claim/apply");
-  m.def("emb_bwd_rowwise_adagrad_fused_wide",
-        &emb_bwd_rowwise_adagrad_fused_wide,
-        "Deep row-wise sparse Adagrad + wide sparse Adagrad (shared ids)");
-  m.def("emb_bwd_rowwise_adagrad_ftrl_fused_wide",
-        &emb_bwd_rowwise_adagrad_ftrl_fused_wide,
-        "Deep row-wise sparse Adagrad + wide sparse FTRL (shared ids)");
+  m.def("emb_bwd_sparse", &emb_bwd_sparse,
+        "Stateful sparse update (adagrad, ftrl, rowwise_adagrad) of a deep "
+        "side, a wide side or both from shared ids: atomic accumulate + "
+        "once-per-row claim/apply; sides without gradients run the apply "
+        "alone on their accumulators",
+        py::arg("deep"), py::arg("wide"), py::arg("stamp"), py::arg("ids"),
+        py::arg("epoch"), py::arg("scale"));
+  m.def("sparse_pair_fused_ok", &sparse_pair_fused_ok,
+        "Whether emb_bwd_sparse has a fused deep+wide kernel for (deep rule, "
+        "wide rule, deep dim)");
   m.def("fused_ftrl", &fused_ftrl, "Fused dense FTRL-proximal step");
   m.def("bias_relu_fwd", &bias_relu_fwd, "Fused bias+ReLU forward");
   m.def("bias_relu_bwd", &bias_relu_bwd, "Fused ReLU backward");

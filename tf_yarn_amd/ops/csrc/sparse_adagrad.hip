@@ -29,7 +29,13 @@
 //                          gradient, s[kStates] the states, w the weight.
 // AdagradRule (1 state) and FtrlRule (2 states) are instantiated.  That
 // interface is per ELEMENT with table-shaped states: lazy Adam would be one
-// more such struct plus entry points; row-wise Adagrad is not.
+// more such struct, its line in kRules and one line in kDispatch per pair
+// wanted; row-wise Adagrad is not.
+//
+// Entry points: emb_bwd_sparse, the one update entry (a deep side, a wide
+// side or both; with gradients pass 1 + pass 2, without them pass 2 alone),
+// and sparse_pair_fused_ok, which answers from the same kDispatch table
+// whether a (deep rule, wide rule, dim) has a fused deep+wide kernel.
 //
 // Row-wise Adagrad keeps ONE fp32 accumulator per row, state_row[rows]:
 //   m = (sum_c G[u, c]^2) / dim;  state_row[u] += m;
@@ -56,6 +62,9 @@
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <string>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 #include "common.h"
 
@@ -306,9 +315,57 @@ __global__ void rowwise_adagrad_apply_row_kernel(
   }
 }
 
-// ---- host: checks -----------------------------------------------------------
+// ---- host: one table's side of an update ------------------------------------
 
 using Tensors = std::vector<torch::Tensor>;
+
+enum RuleId { kAdagrad, kFtrl, kRowwiseAdagrad, kNoRule };
+
+// What the host knows about a rule: its name, how many state tensors it
+// takes, and whether a state holds one value per table row ([rows], row-wise
+// Adagrad) instead of being shaped like the table.
+struct RuleInfo {
+  const char* name;
+  RuleId id;
+  size_t n_states;
+  bool row_state;
+};
+
+const RuleInfo kRules[] = {
+    {"adagrad", kAdagrad, 1, false},
+    {"ftrl", kFtrl, 2, false},
+    {"rowwise_adagrad", kRowwiseAdagrad, 1, true},
+};
+
+const RuleInfo& rule_named(const std::string& name) {
+  for (const auto& r : kRules)
+    if (name == r.name) return r;
+  TORCH_CHECK(false, "unknown sparse rule '", name, "'");
+  return kRules[0];
+}
+
+// A side as the entry point takes it: (rule name, table, the rule's state
+// tensors in the rule's order, accumulator, gradient or None, lr, eps, l1,
+// l2).  A rule reads the scalars it has and ignores the others.
+using SideArg = std::tuple<std::string, torch::Tensor, Tensors,
+                           torch::Tensor, c10::optional<torch::Tensor>,
+                           double, double, double, double>;
+
+struct Side {
+  const RuleInfo* rule;
+  torch::Tensor table;
+  Tensors states;
+  torch::Tensor acc;
+  c10::optional<torch::Tensor> grad;
+  double lr, eps, l1, l2;
+};
+
+Side unpack(const SideArg& arg) {
+  const auto& [rule, table, states, acc, grad, lr, eps, l1, l2] = arg;
+  return {&rule_named(rule), table, states, acc, grad, lr, eps, l1, l2};
+}
+
+// ---- host: checks -----------------------------------------------------------
 
 void check_f32_like(const torch::Tensor& t, const torch::Tensor& table,
                     const char* name) {
@@ -350,41 +407,42 @@ int quad_shift(int64_t dim) {
   return s;
 }
 
-// `states`: the rule's state tensors, in the rule's order
-void check_apply(const torch::Tensor& table, const Tensors& states,
-                 const torch::Tensor& acc, const torch::Tensor& stamp,
-                 const torch::Tensor& ids, int64_t epoch) {
-  TORCH_CHECK(table.is_cuda() && table.is_contiguous() &&
-              table.dim() == 2 && table.scalar_type() == torch::kFloat32,
-              "table must be a contiguous 2D fp32 GPU tensor");
-  for (const auto& s : states) check_f32_like(s, table, "state");
-  check_f32_like(acc, table, "acc");
+// One side's scalars, table, states and accumulator.  deep_rows < 0: the
+// table whose rows are claimed (2D, any dim); otherwise the wide companion
+// of a deep table with that many rows.
+void check_side(const Side& s, int64_t deep_rows) {
+  const bool companion = deep_rows >= 0;
+  if (s.rule->id == kFtrl) check_ftrl_args(s.lr, s.l1, s.l2);
+  if (companion) {
+    TORCH_CHECK(s.table.is_cuda() && s.table.is_contiguous() &&
+                s.table.scalar_type() == torch::kFloat32 &&
+                s.table.numel() == deep_rows, "bad wide table");
+  } else {
+    TORCH_CHECK(s.table.is_cuda() && s.table.is_contiguous() &&
+                s.table.dim() == 2 &&
+                s.table.scalar_type() == torch::kFloat32,
+                "table must be a contiguous 2D fp32 GPU tensor");
+  }
+  TORCH_CHECK(s.states.size() == s.rule->n_states, s.rule->name, " takes ",
+              s.rule->n_states, " state tensor(s), got ", s.states.size());
+  for (const auto& st : s.states) {
+    if (s.rule->row_state) check_row_state(st, s.table);
+    else check_f32_like(st, s.table, companion ? "wide state" : "state");
+  }
+  check_f32_like(s.acc, s.table, companion ? "wide_acc" : "acc");
+}
+
+void check_claim(const torch::Tensor& stamp, const torch::Tensor& ids,
+                 int64_t epoch, int64_t rows) {
   TORCH_CHECK(stamp.is_cuda() && stamp.is_contiguous() &&
               stamp.scalar_type() == torch::kInt32 &&
-              stamp.numel() == table.size(0),
+              stamp.numel() == rows,
               "stamp must be contiguous int32 on GPU, one per table row");
   TORCH_CHECK(ids.is_cuda() && ids.is_contiguous() &&
               ids.scalar_type() == torch::kInt64,
               "ids must be contiguous int64 on GPU");
   TORCH_CHECK(epoch >= 1 && epoch < INT32_MAX,
               "epoch must be in [1, 2^31 - 1)");
-}
-
-void check_apply_fused_wide(
-    const torch::Tensor& table, const Tensors& states,
-    const torch::Tensor& acc, const torch::Tensor& wide_table,
-    const Tensors& wide_states, const torch::Tensor& wide_acc,
-    const torch::Tensor& stamp, const torch::Tensor& ids, int64_t epoch) {
-  check_apply(table, states, acc, stamp, ids, epoch);
-  TORCH_CHECK(wide_table.is_cuda() && wide_table.is_contiguous() &&
-              wide_table.scalar_type() == torch::kFloat32 &&
-              wide_table.numel() == table.size(0), "bad wide table");
-  for (const auto& s : wide_states)
-    check_f32_like(s, wide_table, "wide state");
-  check_f32_like(wide_acc, wide_table, "wide_acc");
-  TORCH_CHECK(quad_shift(table.size(1)) >= 0,
-              "the fused deep+wide apply needs dim/4 to be a power of two "
-              "<= 64");
 }
 
 void check_deep_grad(const torch::Tensor& table, const torch::Tensor& ids,
@@ -410,62 +468,12 @@ void check_pair_grads(const torch::Tensor& table, const torch::Tensor& ids,
               ids.numel() % gw.numel() == 0, "gw dtype/shape mismatch");
 }
 
-// ---- host: launches (inputs already checked) --------------------------------
+// ---- host: pass-2 launches (inputs already checked) -------------------------
 
 template <int N> StatePtrs<N> state_ptrs(const Tensors& states) {
   StatePtrs<N> p{};
   for (int k = 0; k < N; ++k) p.p[k] = states[k].data_ptr<float>();
   return p;
-}
-
-template <typename Rule>
-void launch_apply(torch::Tensor& table, const Tensors& states,
-                  torch::Tensor& acc, torch::Tensor& stamp,
-                  torch::Tensor& ids, int64_t epoch,
-                  typename Rule::Args a) {
-  const int64_t dim = table.size(1);
-  const int64_t n = ids.numel();
-  if (n == 0) return;
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const auto st = state_ptrs<Rule::kStates>(states);
-  const int shift = quad_shift(dim);
-  if (shift >= 0) {
-    int grid = miyarn_grid_cap(n << shift, 8192);
-    hipLaunchKernelGGL((sparse_adagrad_apply_kernel<Rule, NoRule>),
-                       dim3(grid), dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(), st, acc.data_ptr<float>(),
-                       (float*)nullptr, StatePtrs<0>{}, (float*)nullptr,
-                       stamp.data_ptr<int>(), ids.data_ptr<int64_t>(), n,
-                       shift, (int)epoch, a, NoRule::Args{});
-  } else {
-    int grid = miyarn_grid_cap(n, 8192);
-    hipLaunchKernelGGL(sparse_adagrad_apply_row_kernel<Rule>, dim3(grid),
-                       dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(), st, acc.data_ptr<float>(),
-                       stamp.data_ptr<int>(), ids.data_ptr<int64_t>(), n,
-                       dim, (int)epoch, a);
-  }
-}
-
-template <typename Rule, typename WideRule>
-void launch_apply_fused_wide(
-    torch::Tensor& table, const Tensors& states, torch::Tensor& acc,
-    torch::Tensor& wide_table, const Tensors& wide_states,
-    torch::Tensor& wide_acc, torch::Tensor& stamp, torch::Tensor& ids,
-    int64_t epoch, typename Rule::Args a, typename WideRule::Args wa) {
-  const int64_t n = ids.numel();
-  if (n == 0) return;
-  const int shift = quad_shift(table.size(1));
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  int grid = miyarn_grid_cap(n << shift, 8192);
-  hipLaunchKernelGGL((sparse_adagrad_apply_kernel<Rule, WideRule>),
-                     dim3(grid), dim3(MIYARN_BLOCK), 0, stream,
-                     table.data_ptr<float>(),
-                     state_ptrs<Rule::kStates>(states),
-                     acc.data_ptr<float>(), wide_table.data_ptr<float>(),
-                     state_ptrs<WideRule::kStates>(wide_states),
-                     wide_acc.data_ptr<float>(), stamp.data_ptr<int>(),
-                     ids.data_ptr<int64_t>(), n, shift, (int)epoch, a, wa);
 }
 
 AdagradRule::Args adagrad_args(double lr, double eps) {
@@ -476,348 +484,187 @@ FtrlRule::Args ftrl_args(double lr, double l1, double l2) {
   return {(float)lr, (float)l1, (float)l2};
 }
 
-// ---- row-wise Adagrad: checks and launches ----------------------------------
-
-void check_rowwise_apply(const torch::Tensor& table,
-                         const torch::Tensor& state_row,
-                         const torch::Tensor& acc,
-                         const torch::Tensor& stamp,
-                         const torch::Tensor& ids, int64_t epoch) {
-  check_apply(table, {}, acc, stamp, ids, epoch);
-  check_row_state(state_row, table);
+template <typename Rule> typename Rule::Args rule_args(const Side& s);
+template <> AdagradRule::Args rule_args<AdagradRule>(const Side& s) {
+  return adagrad_args(s.lr, s.eps);
+}
+template <> FtrlRule::Args rule_args<FtrlRule>(const Side& s) {
+  return ftrl_args(s.lr, s.l1, s.l2);
 }
 
-void check_rowwise_apply_fused_wide(
-    const torch::Tensor& table, const torch::Tensor& state_row,
-    const torch::Tensor& acc, const torch::Tensor& wide_table,
-    const Tensors& wide_states, const torch::Tensor& wide_acc,
-    const torch::Tensor& stamp, const torch::Tensor& ids, int64_t epoch) {
-  check_apply_fused_wide(table, {}, acc, wide_table, wide_states, wide_acc,
-                         stamp, ids, epoch);
-  check_row_state(state_row, table);
+// The wide companion's kernel arguments; all null under NoRule.
+template <typename WideRule> struct WideArgs {
+  float* table = nullptr;
+  StatePtrs<WideRule::kStates> state{};
+  float* acc = nullptr;
+  typename WideRule::Args a{};
+};
+
+template <typename WideRule> WideArgs<WideRule> wide_args(const Side* w) {
+  WideArgs<WideRule> out;
+  if constexpr (WideRule::kStates > 0) {
+    out.table = w->table.data_ptr<float>();
+    out.state = state_ptrs<WideRule::kStates>(w->states);
+    out.acc = w->acc.data_ptr<float>();
+    out.a = rule_args<WideRule>(*w);
+  }
+  return out;
 }
 
-void launch_rowwise_apply(torch::Tensor& table, torch::Tensor& state_row,
-                          torch::Tensor& acc, torch::Tensor& stamp,
-                          torch::Tensor& ids, int64_t epoch,
-                          AdagradRule::Args a) {
-  const int64_t dim = table.size(1);
+// An element-wise rule on `d`, with the wide companion `w` under WideRule
+// (NoRule: w == nullptr, and dims off the quad map take the row kernel).
+template <typename Rule, typename WideRule>
+void launch_elementwise(const Side& d, const Side* w,
+                        const torch::Tensor& stamp, const torch::Tensor& ids,
+                        int64_t epoch) {
+  const int64_t dim = d.table.size(1);
   const int64_t n = ids.numel();
   if (n == 0) return;
   auto stream = c10::hip::getCurrentHIPStream().stream();
+  const auto st = state_ptrs<Rule::kStates>(d.states);
+  const auto a = rule_args<Rule>(d);
   const int shift = quad_shift(dim);
   if (shift >= 0) {
+    const auto wd = wide_args<WideRule>(w);
     int grid = miyarn_grid_cap(n << shift, 8192);
-    hipLaunchKernelGGL(rowwise_adagrad_apply_kernel<NoRule>, dim3(grid),
-                       dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(), state_row.data_ptr<float>(),
-                       acc.data_ptr<float>(), (float*)nullptr,
-                       StatePtrs<0>{}, (float*)nullptr,
+    hipLaunchKernelGGL((sparse_adagrad_apply_kernel<Rule, WideRule>),
+                       dim3(grid), dim3(MIYARN_BLOCK), 0, stream,
+                       d.table.data_ptr<float>(), st,
+                       d.acc.data_ptr<float>(), wd.table, wd.state, wd.acc,
                        stamp.data_ptr<int>(), ids.data_ptr<int64_t>(), n,
-                       shift, (int)epoch, a, NoRule::Args{});
-  } else {
+                       shift, (int)epoch, a, wd.a);
+  } else if constexpr (std::is_same_v<WideRule, NoRule>) {
     int grid = miyarn_grid_cap(n, 8192);
-    hipLaunchKernelGGL(rowwise_adagrad_apply_row_kernel, dim3(grid),
+    hipLaunchKernelGGL(sparse_adagrad_apply_row_kernel<Rule>, dim3(grid),
                        dim3(MIYARN_BLOCK), 0, stream,
-                       table.data_ptr<float>(), state_row.data_ptr<float>(),
-                       acc.data_ptr<float>(), stamp.data_ptr<int>(),
+                       d.table.data_ptr<float>(), st,
+                       d.acc.data_ptr<float>(), stamp.data_ptr<int>(),
                        ids.data_ptr<int64_t>(), n, dim, (int)epoch, a);
+  } else {
+    TORCH_INTERNAL_ASSERT(false, "pair at a dim off the quad map");
   }
 }
 
+// Row-wise Adagrad on `d`, companion as above.
 template <typename WideRule>
-void launch_rowwise_apply_fused_wide(
-    torch::Tensor& table, torch::Tensor& state_row, torch::Tensor& acc,
-    torch::Tensor& wide_table, const Tensors& wide_states,
-    torch::Tensor& wide_acc, torch::Tensor& stamp, torch::Tensor& ids,
-    int64_t epoch, AdagradRule::Args a, typename WideRule::Args wa) {
+void launch_rowwise(const Side& d, const Side* w, const torch::Tensor& stamp,
+                    const torch::Tensor& ids, int64_t epoch) {
+  const int64_t dim = d.table.size(1);
   const int64_t n = ids.numel();
   if (n == 0) return;
-  const int shift = quad_shift(table.size(1));
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  int grid = miyarn_grid_cap(n << shift, 8192);
-  hipLaunchKernelGGL(rowwise_adagrad_apply_kernel<WideRule>, dim3(grid),
-                     dim3(MIYARN_BLOCK), 0, stream,
-                     table.data_ptr<float>(), state_row.data_ptr<float>(),
-                     acc.data_ptr<float>(), wide_table.data_ptr<float>(),
-                     state_ptrs<WideRule::kStates>(wide_states),
-                     wide_acc.data_ptr<float>(), stamp.data_ptr<int>(),
-                     ids.data_ptr<int64_t>(), n, shift, (int)epoch, a, wa);
+  float* state_row = d.states[0].data_ptr<float>();
+  const auto a = rule_args<AdagradRule>(d);
+  const int shift = quad_shift(dim);
+  if (shift >= 0) {
+    const auto wd = wide_args<WideRule>(w);
+    int grid = miyarn_grid_cap(n << shift, 8192);
+    hipLaunchKernelGGL(rowwise_adagrad_apply_kernel<WideRule>, dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       d.table.data_ptr<float>(), state_row,
+                       d.acc.data_ptr<float>(), wd.table, wd.state, wd.acc,
+                       stamp.data_ptr<int>(), ids.data_ptr<int64_t>(), n,
+                       shift, (int)epoch, a, wd.a);
+  } else if constexpr (std::is_same_v<WideRule, NoRule>) {
+    int grid = miyarn_grid_cap(n, 8192);
+    hipLaunchKernelGGL(rowwise_adagrad_apply_row_kernel, dim3(grid),
+                       dim3(MIYARN_BLOCK), 0, stream,
+                       d.table.data_ptr<float>(), state_row,
+                       d.acc.data_ptr<float>(), stamp.data_ptr<int>(),
+                       ids.data_ptr<int64_t>(), n, dim, (int)epoch, a);
+  } else {
+    TORCH_INTERNAL_ASSERT(false, "pair at a dim off the quad map");
+  }
+}
+
+// ---- host: the dispatch -----------------------------------------------------
+
+// Every pass-2 instantiation there is, by (deep rule, wide rule); kNoRule:
+// one table alone, deep or wide.  A pair that is not listed has no fused
+// kernel: the entry point refuses it and sparse_pair_fused_ok says so.
+// A new pair is one line here.
+struct Dispatch {
+  RuleId deep, wide;
+  void (*launch)(const Side& d, const Side* w, const torch::Tensor& stamp,
+                 const torch::Tensor& ids, int64_t epoch);
+};
+
+const Dispatch kDispatch[] = {
+    {kAdagrad, kNoRule, launch_elementwise<AdagradRule, NoRule>},
+    {kFtrl, kNoRule, launch_elementwise<FtrlRule, NoRule>},
+    {kRowwiseAdagrad, kNoRule, launch_rowwise<NoRule>},
+    {kAdagrad, kAdagrad, launch_elementwise<AdagradRule, AdagradRule>},
+    {kAdagrad, kFtrl, launch_elementwise<AdagradRule, FtrlRule>},
+    {kFtrl, kFtrl, launch_elementwise<FtrlRule, FtrlRule>},
+    {kRowwiseAdagrad, kAdagrad, launch_rowwise<AdagradRule>},
+    {kRowwiseAdagrad, kFtrl, launch_rowwise<FtrlRule>},
+};
+
+const Dispatch* find_dispatch(RuleId deep, RuleId wide) {
+  for (const auto& k : kDispatch)
+    if (k.deep == deep && k.wide == wide) return &k;
+  return nullptr;
 }
 
 }  // namespace
 
-// ---- pass 2 alone (acc already holds the summed, scaled gradient) ---------
-
-void sparse_adagrad_apply(torch::Tensor table, torch::Tensor state_sum,
-                          torch::Tensor acc, torch::Tensor stamp,
-                          torch::Tensor ids, int64_t epoch, double lr,
-                          double eps) {
-  check_apply(table, {state_sum}, acc, stamp, ids, epoch);
-  launch_apply<AdagradRule>(table, {state_sum}, acc, stamp, ids, epoch,
-                            adagrad_args(lr, eps));
+// Whether the (deep, wide) rule pair has a fused deep+wide kernel at this
+// deep dim: the pair is in kDispatch and dim/4 is a power of two <= 64.
+bool sparse_pair_fused_ok(const std::string& deep_rule,
+                          const std::string& wide_rule, int64_t dim) {
+  return find_dispatch(rule_named(deep_rule).id, rule_named(wide_rule).id) &&
+         quad_shift(dim) >= 0;
 }
 
-void sparse_adagrad_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    int64_t epoch, double lr, double eps) {
-  check_apply_fused_wide(table, {state_sum}, acc, wide_table, {wide_state},
-                         wide_acc, stamp, ids, epoch);
-  launch_apply_fused_wide<AdagradRule, AdagradRule>(
-      table, {state_sum}, acc, wide_table, {wide_state}, wide_acc, stamp,
-      ids, epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
-}
-
-void sparse_ftrl_apply(torch::Tensor table, torch::Tensor accum,
-                       torch::Tensor linear, torch::Tensor acc,
-                       torch::Tensor stamp, torch::Tensor ids,
-                       int64_t epoch, double lr, double l1, double l2) {
-  check_ftrl_args(lr, l1, l2);
-  check_apply(table, {accum, linear}, acc, stamp, ids, epoch);
-  launch_apply<FtrlRule>(table, {accum, linear}, acc, stamp, ids, epoch,
-                         ftrl_args(lr, l1, l2));
-}
-
-// deep Adagrad (lr, eps) + wide FTRL (wide_lr, l1, l2)
-void sparse_adagrad_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double eps,
-    double wide_lr, double l1, double l2) {
-  check_ftrl_args(wide_lr, l1, l2);
-  check_apply_fused_wide(table, {state_sum}, acc, wide_table,
-                         {wide_accum, wide_linear}, wide_acc, stamp, ids,
-                         epoch);
-  launch_apply_fused_wide<AdagradRule, FtrlRule>(
-      table, {state_sum}, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
-      ftrl_args(wide_lr, l1, l2));
-}
-
-// deep FTRL (lr, l1, l2) + wide FTRL (wide_lr, l1, l2)
-void sparse_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
-    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double wide_lr, double l1,
-    double l2) {
-  check_ftrl_args(lr, l1, l2);
-  check_ftrl_args(wide_lr, l1, l2);
-  check_apply_fused_wide(table, {accum, linear}, acc, wide_table,
-                         {wide_accum, wide_linear}, wide_acc, stamp, ids,
-                         epoch);
-  launch_apply_fused_wide<FtrlRule, FtrlRule>(
-      table, {accum, linear}, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, ftrl_args(lr, l1, l2),
-      ftrl_args(wide_lr, l1, l2));
-}
-
-// row-wise Adagrad, single table
-void sparse_rowwise_adagrad_apply(torch::Tensor table,
-                                  torch::Tensor state_row,
-                                  torch::Tensor acc, torch::Tensor stamp,
-                                  torch::Tensor ids, int64_t epoch,
-                                  double lr, double eps) {
-  check_rowwise_apply(table, state_row, acc, stamp, ids, epoch);
-  launch_rowwise_apply(table, state_row, acc, stamp, ids, epoch,
-                       adagrad_args(lr, eps));
-}
-
-// deep row-wise Adagrad + wide Adagrad, one (lr, eps)
-void sparse_rowwise_adagrad_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    int64_t epoch, double lr, double eps) {
-  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
-                                 {wide_state}, wide_acc, stamp, ids, epoch);
-  launch_rowwise_apply_fused_wide<AdagradRule>(
-      table, state_row, acc, wide_table, {wide_state}, wide_acc, stamp, ids,
-      epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
-}
-
-// deep row-wise Adagrad (lr, eps) + wide FTRL (wide_lr, l1, l2)
-void sparse_rowwise_adagrad_ftrl_apply_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, int64_t epoch, double lr, double eps,
-    double wide_lr, double l1, double l2) {
-  check_ftrl_args(wide_lr, l1, l2);
-  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
-                                 {wide_accum, wide_linear}, wide_acc, stamp,
-                                 ids, epoch);
-  launch_rowwise_apply_fused_wide<FtrlRule>(
-      table, state_row, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
-      ftrl_args(wide_lr, l1, l2));
-}
-
-// ---- pass 1 + pass 2: every input is validated before anything launches ---
-
-// table[u] over the unique ids u: G = scale * sum of grad rows,
-// state += G^2, table -= lr * G / (sqrt(state) + eps).
-void emb_bwd_adagrad(torch::Tensor table, torch::Tensor state_sum,
-                     torch::Tensor acc, torch::Tensor stamp,
-                     torch::Tensor ids, torch::Tensor grad, int64_t epoch,
-                     double lr, double eps, double scale) {
-  check_apply(table, {state_sum}, acc, stamp, ids, epoch);
-  check_deep_grad(table, ids, grad);
-  emb_bwd_dense(acc, ids, grad, scale);
-  launch_apply<AdagradRule>(table, {state_sum}, acc, stamp, ids, epoch,
-                            adagrad_args(lr, eps));
-}
-
-// Wide companion: [rows, 1] table, per-example gradient gw with the
-// gw[i / g_div] layout of emb_scatter_sum (g_div = ids.numel()/gw.numel()).
-void emb_bwd_adagrad_wide(torch::Tensor table, torch::Tensor state_sum,
-                          torch::Tensor acc, torch::Tensor stamp,
-                          torch::Tensor ids, torch::Tensor gw,
-                          int64_t epoch, double lr, double eps,
-                          double scale) {
-  check_apply(table, {state_sum}, acc, stamp, ids, epoch);
-  check_wide_grad(table, ids, gw);
-  if (ids.numel() == 0) return;
-  emb_scatter_sum(acc, ids, gw, scale);
-  launch_apply<AdagradRule>(table, {state_sum}, acc, stamp, ids, epoch,
-                            adagrad_args(lr, eps));
-}
-
-// Deep + wide pair from one pass over the shared flat ids per phase.
-void emb_bwd_adagrad_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
-    double eps, double scale) {
-  check_apply_fused_wide(table, {state_sum}, acc, wide_table, {wide_state},
-                         wide_acc, stamp, ids, epoch);
-  check_pair_grads(table, ids, grad, gw);
-  // lr = -1 turns the fused SGD scatter into acc += scale * g
-  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
-  launch_apply_fused_wide<AdagradRule, AdagradRule>(
-      table, {state_sum}, acc, wide_table, {wide_state}, wide_acc, stamp,
-      ids, epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
-}
-
-// FTRL-proximal on the unique ids u: G as above, then FtrlRule::one per
-// element on (accum, linear, table).
-void emb_bwd_ftrl(torch::Tensor table, torch::Tensor accum,
-                  torch::Tensor linear, torch::Tensor acc,
-                  torch::Tensor stamp, torch::Tensor ids,
-                  torch::Tensor grad, int64_t epoch, double lr, double l1,
-                  double l2, double scale) {
-  check_ftrl_args(lr, l1, l2);
-  check_apply(table, {accum, linear}, acc, stamp, ids, epoch);
-  check_deep_grad(table, ids, grad);
-  emb_bwd_dense(acc, ids, grad, scale);
-  launch_apply<FtrlRule>(table, {accum, linear}, acc, stamp, ids, epoch,
-                         ftrl_args(lr, l1, l2));
-}
-
-void emb_bwd_ftrl_wide(torch::Tensor table, torch::Tensor accum,
-                       torch::Tensor linear, torch::Tensor acc,
-                       torch::Tensor stamp, torch::Tensor ids,
-                       torch::Tensor gw, int64_t epoch, double lr,
-                       double l1, double l2, double scale) {
-  check_ftrl_args(lr, l1, l2);
-  check_apply(table, {accum, linear}, acc, stamp, ids, epoch);
-  check_wide_grad(table, ids, gw);
-  if (ids.numel() == 0) return;
-  emb_scatter_sum(acc, ids, gw, scale);
-  launch_apply<FtrlRule>(table, {accum, linear}, acc, stamp, ids, epoch,
-                         ftrl_args(lr, l1, l2));
-}
-
-// The flagship pair: deep Adagrad + wide FTRL, shared flat ids.
-void emb_bwd_adagrad_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor state_sum, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double eps, double wide_lr, double l1, double l2,
-    double scale) {
-  check_ftrl_args(wide_lr, l1, l2);
-  check_apply_fused_wide(table, {state_sum}, acc, wide_table,
-                         {wide_accum, wide_linear}, wide_acc, stamp, ids,
-                         epoch);
-  check_pair_grads(table, ids, grad, gw);
-  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
-  launch_apply_fused_wide<AdagradRule, FtrlRule>(
-      table, {state_sum}, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
-      ftrl_args(wide_lr, l1, l2));
-}
-
-void emb_bwd_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor accum, torch::Tensor linear,
-    torch::Tensor acc, torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double wide_lr, double l1, double l2, double scale) {
-  check_ftrl_args(lr, l1, l2);
-  check_ftrl_args(wide_lr, l1, l2);
-  check_apply_fused_wide(table, {accum, linear}, acc, wide_table,
-                         {wide_accum, wide_linear}, wide_acc, stamp, ids,
-                         epoch);
-  check_pair_grads(table, ids, grad, gw);
-  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
-  launch_apply_fused_wide<FtrlRule, FtrlRule>(
-      table, {accum, linear}, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, ftrl_args(lr, l1, l2),
-      ftrl_args(wide_lr, l1, l2));
-}
-
-// Row-wise Adagrad on the unique ids u: G as above, m = sum_c G[u, c]^2 /
-// dim, state_row[u] += m, table[u, :] -= lr * G[u, :] / (sqrt(state_row[u])
-// + eps).
-void emb_bwd_rowwise_adagrad(torch::Tensor table, torch::Tensor state_row,
-                             torch::Tensor acc, torch::Tensor stamp,
-                             torch::Tensor ids, torch::Tensor grad,
-                             int64_t epoch, double lr, double eps,
-                             double scale) {
-  check_rowwise_apply(table, state_row, acc, stamp, ids, epoch);
-  check_deep_grad(table, ids, grad);
-  emb_bwd_dense(acc, ids, grad, scale);
-  launch_rowwise_apply(table, state_row, acc, stamp, ids, epoch,
-                       adagrad_args(lr, eps));
-}
-
-// deep row-wise Adagrad + wide Adagrad, shared flat ids
-void emb_bwd_rowwise_adagrad_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_state,
-    torch::Tensor wide_acc, torch::Tensor stamp, torch::Tensor ids,
-    torch::Tensor grad, torch::Tensor gw, int64_t epoch, double lr,
-    double eps, double scale) {
-  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
-                                 {wide_state}, wide_acc, stamp, ids, epoch);
-  check_pair_grads(table, ids, grad, gw);
-  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
-  launch_rowwise_apply_fused_wide<AdagradRule>(
-      table, state_row, acc, wide_table, {wide_state}, wide_acc, stamp, ids,
-      epoch, adagrad_args(lr, eps), adagrad_args(lr, eps));
-}
-
-// The recipe with a row-wise deep table: + wide FTRL, shared flat ids.
-void emb_bwd_rowwise_adagrad_ftrl_fused_wide(
-    torch::Tensor table, torch::Tensor state_row, torch::Tensor acc,
-    torch::Tensor wide_table, torch::Tensor wide_accum,
-    torch::Tensor wide_linear, torch::Tensor wide_acc, torch::Tensor stamp,
-    torch::Tensor ids, torch::Tensor grad, torch::Tensor gw, int64_t epoch,
-    double lr, double eps, double wide_lr, double l1, double l2,
-    double scale) {
-  check_ftrl_args(wide_lr, l1, l2);
-  check_rowwise_apply_fused_wide(table, state_row, acc, wide_table,
-                                 {wide_accum, wide_linear}, wide_acc, stamp,
-                                 ids, epoch);
-  check_pair_grads(table, ids, grad, gw);
-  emb_bwd_sgd_fused_wide(acc, wide_acc, ids, grad, gw, -1.0, scale);
-  launch_rowwise_apply_fused_wide<FtrlRule>(
-      table, state_row, acc, wide_table, {wide_accum, wide_linear},
-      wide_acc, stamp, ids, epoch, adagrad_args(lr, eps),
-      ftrl_args(wide_lr, l1, l2));
+// The stateful sparse update of one table (deep or wide side alone) or of a
+// deep table and its [rows, 1] wide companion from their shared flat ids.
+// On the unique ids u, G = scale * sum of the gradient rows; then the side's
+// rule, once per row:
+//   adagrad          state += G^2, table -= lr * G / (sqrt(state) + eps)
+//   ftrl             FtrlRule::one per element on (accum, linear, table)
+//   rowwise_adagrad  state_row[u] += sum_c G[u, c]^2 / dim,
+//                    table[u, :] -= lr * G[u, :] / (sqrt(state_row[u]) + eps)
+// The wide gradient is per example, in the gw[i / g_div] layout of
+// emb_scatter_sum (g_div = ids.numel() / gw.numel()).  Sides without
+// gradients run pass 2 alone: their accumulators already hold G.
+// Every input is validated, then pass 1 runs, then pass 2.
+void emb_bwd_sparse(c10::optional<SideArg> deep, c10::optional<SideArg> wide,
+                    torch::Tensor stamp, torch::Tensor ids, int64_t epoch,
+                    double scale) {
+  TORCH_CHECK(deep || wide, "emb_bwd_sparse needs a deep or a wide side");
+  if (deep && wide) {
+    const Side d = unpack(*deep), w = unpack(*wide);
+    const Dispatch* k = find_dispatch(d.rule->id, w.rule->id);
+    TORCH_CHECK(k, "no fused deep+wide kernel for the pair (", d.rule->name,
+                ", ", w.rule->name, ")");
+    check_side(d, -1);
+    check_claim(stamp, ids, epoch, d.table.size(0));
+    check_side(w, d.table.size(0));
+    TORCH_CHECK(quad_shift(d.table.size(1)) >= 0,
+                "the fused deep+wide apply needs dim/4 to be a power of two "
+                "<= 64");
+    TORCH_CHECK(d.grad.has_value() == w.grad.has_value(),
+                "a pair takes both gradients or neither");
+    if (d.grad) {
+      check_pair_grads(d.table, ids, *d.grad, *w.grad);
+      // lr = -1 turns the fused SGD scatter into acc += scale * g
+      emb_bwd_sgd_fused_wide(d.acc, w.acc, ids, *d.grad, *w.grad, -1.0,
+                             scale);
+    }
+    k->launch(d, &w, stamp, ids, epoch);
+    return;
+  }
+  const Side s = unpack(deep ? *deep : *wide);
+  check_side(s, -1);
+  check_claim(stamp, ids, epoch, s.table.size(0));
+  if (s.grad) {
+    if (deep) check_deep_grad(s.table, ids, *s.grad);
+    else check_wide_grad(s.table, ids, *s.grad);
+  }
+  if (wide && ids.numel() == 0) return;
+  if (s.grad) {
+    if (deep) emb_bwd_dense(s.acc, ids, *s.grad, scale);
+    else emb_scatter_sum(s.acc, ids, *s.grad, scale);
+  }
+  find_dispatch(s.rule->id, kNoRule)->launch(s, nullptr, stamp, ids, epoch);
 }
