@@ -83,15 +83,7 @@ def wgrad_b_sweep():
 
 def custom_wgrad():
     import tf_yarn_amd.ops._C as C
-    for (cin, cout) in LAYERS_PAD:
-        x = torch.randn(B, cin, device="cuda").to(torch.bfloat16)
-        dy = torch.randn(B, cout, device="cuda").to(torch.bfloat16)
-        for sk in (2, 4, 8, 16):
-            t = timeit(lambda: C.wgrad_nt(dy, x, sk))
-            gf = 2 * B * cin * cout / 1e9
-            print(f"[custom wgrad {cout}x{cin} sk={sk:2}] {t:7.1f}us "
-                  f"({gf/t*1e3:5.0f} TF)")
-    for (cin, cout) in [(432, 1024)] + LAYERS_PAD[1:]:
+    for (cin, cout) in LAYERS:
         x = torch.randn(B, cin, device="cuda").to(torch.bfloat16)
         dy = torch.randn(B, cout, device="cuda").to(torch.bfloat16)
         for sk in (4, 8, 16, 32):
@@ -157,8 +149,6 @@ def custom_fwd():
               f"({gf/t_cus*1e3:5.0f} TF)  +transpose {t_cus_t:7.1f}us  "
               f"relerr {rel:.3e}")
 
-
-LAYERS_PAD = [(448, 1024), (1024, 512), (512, 256)]
 
 if __name__ == "__main__":
     assert torch.cuda.is_available()

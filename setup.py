@@ -36,8 +36,6 @@ ext = CUDAExtension(
         os.path.join(CSRC, "sparse_adagrad.hip"),
         os.path.join(CSRC, "elementwise.hip"),
         os.path.join(CSRC, "wgrad.hip"),
-        os.path.join(CSRC, "wgrad128.hip"),
-        os.path.join(CSRC, "wgrad256.hip"),
         os.path.join(CSRC, "gemm_bt.hip"),
         os.path.join(CSRC, "lt_linear.hip"),
     ],

@@ -34,24 +34,22 @@ def _dev(t, dtype):
 
 # ---- 1. split-K MFMA weight gradients --------------------------------------
 
-BK = 64  # k-step of all three kernels (B % 64 == 0 is their precondition)
+BK = 64  # k-step of both kernels (B % 64 == 0 is their precondition)
 
 
 def _wgrad_cases():
     cases = []
-    for name, n0, ms in (("wgrad_nt", 64, (64, 192)),
-                         ("wgrad_nt128", 128, (8, 136, 432)),
+    for name, n0, ms in (("wgrad_nt128", 128, (8, 136, 432)),
                          ("wgrad_nt256", 256, (8, 264, 432))):
-        # B = 65 k-steps: auto split-K leaves a short last slab in the 128
-        # and 256 kernels (22 slabs of 3 steps, the last of 2); splitk=4
-        # does in all three (17+17+17+14 steps)
+        # B = 65 k-steps: auto split-K leaves a short last slab (22 slabs
+        # of 3 steps, the last of 2); so does splitk=4 (17+17+17+14 steps)
         cases += [(name, 65 * BK, n0, ms[0], sk, False) for sk in (0, 4)]
         # B = 3 k-steps: splitk=2 -> slabs of 2+1 steps (short last slab),
         # splitk=100 > B/BK must be clamped to 3 by the host
         cases += [(name, 3 * BK, n0, ms[1], sk, False)
                   for sk in (1, 2, 3, 100)]
         cases.append((name, BK, n0, ms[0], 0, False))  # one k-step in all
-        # M edges (masked column tail of the 128/256 kernels: 8 = one
+        # M edges (masked column tail: 8 = one
         # quad pair, tile+8, 432 = the model's first layer), 3+2 steps
         cases += [(name, 5 * BK, n0, m, 2, False) for m in ms]
         cases.append((name, 5 * BK, 2 * n0, ms[-1], 0, False))  # 2 N-tiles
@@ -82,8 +80,7 @@ def test_wgrad_exact(name, B, N, M, splitk, out_bf16):
 
 
 @requires_gpu
-@pytest.mark.parametrize("name,N,M", [("wgrad_nt", 128, 192),
-                                      ("wgrad_nt128", 256, 432),
+@pytest.mark.parametrize("name,N,M", [("wgrad_nt128", 256, 432),
                                       ("wgrad_nt256", 512, 432)])
 def test_wgrad_position_coded(name, N, M):
     """dy[b, n] = 1 only at b = b0(n), so dW[n, m] = x[b0(n), m]: every

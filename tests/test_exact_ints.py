@@ -41,10 +41,9 @@ def test_fp32_mm_equals_float64_at_bench_depth():
 
 
 def _slabs(name, B, N, M, splitk):
-    """Mirror of the host-side split-K arithmetic of csrc/wgrad*.hip:
+    """Mirror of the host-side split-K arithmetic of csrc/wgrad.hip:
     the k-steps (of 64 batch rows) each slab reduces."""
-    tile, budget, cap = {"wgrad_nt": (64, 512, None),
-                         "wgrad_nt128": (128, 512, 32),
+    tile, budget, cap = {"wgrad_nt128": (128, 512, 32),
                          "wgrad_nt256": (256, 256, 32)}[name]
     tiles = (N // tile) * -(-M // tile)
     if splitk <= 0:
@@ -78,12 +77,9 @@ def test_wgrad_cases_reach_the_short_slab_and_the_clamp():
         if B == 65536:
             kinds.add("depth")
     for name, kinds in seen.items():
-        assert {"short last slab", "clamped", "one slab", "depth"} <= kinds
-        # the 64-tile kernel's auto split gives every k-step its own slab
-        assert ("short last slab, auto split" in kinds) == \
-            (name != "wgrad_nt"), name
+        assert {"short last slab", "short last slab, auto split",
+                "clamped", "one slab", "depth"} <= kinds, name
     assert _slabs("wgrad_nt128", 65 * 64, 128, 8, 0) == [3] * 21 + [2]
-    assert _slabs("wgrad_nt", 3 * 64, 64, 192, 2) == [2, 1]
     assert _slabs("wgrad_nt256", 3 * 64, 256, 264, 100) == [1, 1, 1]
 
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import functools
 import logging
+import os
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -831,7 +832,6 @@ def emb_gather_sum(table: torch.Tensor, ids: torch.Tensor,
 
 def _env_switch_on(name: str) -> bool:
     """A default-on A/B switch: only an empty value or "0" turns it off."""
-    import os
     return os.environ.get(name, "1") not in ("", "0")
 
 
@@ -1095,7 +1095,6 @@ def _custom_wgrad_kernel(dz: torch.Tensor, x: torch.Tensor):
     312/359 TF on the 1024x432 / 512x1024 layers (hipBLASLt in-context ran
     them at ~207 us each); 128^2 tiles win the small 256x512 layer
     (94 us vs ~142-190)."""
-    import os
     if os.environ.get("MIYARN_WGRAD") == "lib":
         return None  # A/B escape hatch: force hipBLASLt
     if not (dz.is_cuda and HAVE_EXT):
@@ -1121,7 +1120,6 @@ def _custom_fwd_ok(x: torch.Tensor, weight: torch.Tensor,
     with only 7-16 K-tile iterations the software pipeline never hits the
     steady state the wgrad kernels reach over B=65536 (scripts/
     micro_gemm.py --fwd)."""
-    import os
     if os.environ.get("MIYARN_FWD") != "custom":
         return False
     if not (x.is_cuda and HAVE_EXT):
@@ -1140,7 +1138,6 @@ def _lt_fwd_ok(x, weight, bias) -> bool:
     library call, no z round trip (the separate epilogue kernel cost
     81 us/step + 470 MB of z traffic at the bench shape).
     MIYARN_LT_FWD=0 restores the torch-matmul + epilogue-kernel path."""
-    import os
     if os.environ.get("MIYARN_LT_FWD", "1") in ("", "0"):
         return False
     return (x.is_cuda and HAVE_EXT and x.dim() == 2
@@ -1150,6 +1147,30 @@ def _lt_fwd_ok(x, weight, bias) -> bool:
             and x.is_contiguous() and weight.is_contiguous())
 
 
+def _linear_bias_relu_fwd(x: torch.Tensor, weight: torch.Tensor,
+                          bias: torch.Tensor) -> torch.Tensor:
+    """``relu(x @ weight.T + bias)`` by the first of: the fused ``gemm_bt``
+    (opt-in), hipBLASLt with the bias+ReLU epilogue, matmul + the
+    ``bias_relu_fwd`` kernel."""
+    if _custom_fwd_ok(x, weight, bias):
+        return _C.gemm_bt(x, weight, bias, True)
+    if _lt_fwd_ok(x, weight, bias):
+        return _C.lt_linear(x, weight, bias.contiguous(), True)
+    return bias_relu_fwd(x.matmul(weight.t()), bias)
+
+
+def _linear_wgrad(dz: torch.Tensor, x: torch.Tensor,
+                  weight: torch.Tensor) -> torch.Tensor:
+    """``dz.T @ x`` in ``weight``'s dtype: the custom split-K kernel where
+    :func:`_custom_wgrad_kernel` picks one (split-K partial sum + cast
+    fused into one reduce kernel), else the library."""
+    kernel = _custom_wgrad_kernel(dz, x)
+    if kernel is None:
+        return dz.t().matmul(x)
+    dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16)
+    return dw if dw.dtype == weight.dtype else dw.to(weight.dtype)
+
+
 class LinearBiasReLU(torch.autograd.Function):
     """y = relu(x @ w.T + bias) with a fully-controlled backward:
     fused dx+dbias kernel, dgrad via hipBLASLt, wgrad via the custom
@@ -1157,13 +1178,7 @@ class LinearBiasReLU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        if _custom_fwd_ok(x, weight, bias):
-            y = _C.gemm_bt(x, weight, bias, True)
-        elif _lt_fwd_ok(x, weight, bias):
-            y = _C.lt_linear(x, weight, bias.contiguous(), True)
-        else:
-            z = x.matmul(weight.t())
-            y = bias_relu_fwd(z, bias)
+        y = _linear_bias_relu_fwd(x, weight, bias)
         ctx.save_for_backward(x, weight, y)
         return y
 
@@ -1181,15 +1196,7 @@ class LinearBiasReLU(torch.autograd.Function):
             dz = bias_relu_bwd(dy, y)
             dbias = dz.sum(dim=tuple(range(dz.dim() - 1)))
         dx = dz.matmul(weight)
-        kernel = _custom_wgrad_kernel(dz, x)
-        if kernel is not None:
-            # split-K partial sum + cast fused into one reduce kernel
-            dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16)
-            if dw.dtype != weight.dtype:
-                dw = dw.to(weight.dtype)
-        else:
-            dw = dz.t().matmul(x)
-        return dx, dw, dbias
+        return dx, _linear_wgrad(dz, x, weight), dbias
 
 
 def linear_bias_relu(x: torch.Tensor, weight: torch.Tensor,
@@ -1262,12 +1269,7 @@ class LinearBiasReLUHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, w_head, b_head):
-        if _custom_fwd_ok(x, weight, bias):
-            y = _C.gemm_bt(x, weight, bias, True)
-        elif _lt_fwd_ok(x, weight, bias):
-            y = _C.lt_linear(x, weight, bias.contiguous(), True)
-        else:
-            y = bias_relu_fwd(x.matmul(weight.t()), bias)
+        y = _linear_bias_relu_fwd(x, weight, bias)
         ctx.save_for_backward(x, weight, y, w_head)
         if _on_gpu(y, w_head) and y.size(1) % 4 == 0 \
                 and y.size(1) <= 512 and b_head.numel() == 1:
@@ -1291,13 +1293,7 @@ class LinearBiasReLUHeadFn(torch.autograd.Function):
                 db_head = dl.sum().reshape(1).to(w_head.dtype)
             dz, dbias = head_relu_bwd_db(dl, w_head, y)
         dx = dz.matmul(weight)
-        kernel = _custom_wgrad_kernel(dz, x)
-        if kernel is not None:
-            dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16)
-            if dw.dtype != weight.dtype:
-                dw = dw.to(weight.dtype)
-        else:
-            dw = dz.t().matmul(x)
+        dw = _linear_wgrad(dz, x, weight)
         return dx, dw, dbias, dw_head, db_head
 
 

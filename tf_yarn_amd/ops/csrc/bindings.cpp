@@ -122,8 +122,6 @@ torch::Tensor bce_head_bwd(torch::Tensor sig, torch::Tensor labels,
                            torch::Tensor g);
 
 // wgrad.hip
-torch::Tensor wgrad_nt(torch::Tensor dy, torch::Tensor x, int64_t splitk,
-                       bool out_bf16);
 torch::Tensor wgrad_nt128(torch::Tensor dy, torch::Tensor x,
                           int64_t splitk, bool out_bf16);
 torch::Tensor wgrad_nt256(torch::Tensor dy, torch::Tensor x,
@@ -188,16 +186,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "reduce_splitk's tall-slab kernel with 1 or 4 quad lanes per block",
         py::arg("part"), py::arg("out_bf16") = false,
         py::arg("quad_lanes") = 1);
-  m.def("wgrad_nt", &wgrad_nt,
-        "Split-K MFMA weight gradient: dW = dy^T @ x (bf16 in)",
-        py::arg("dy"), py::arg("x"), py::arg("splitk"),
-        py::arg("out_bf16") = false);
   m.def("wgrad_nt128", &wgrad_nt128,
-        "Split-K MFMA weight gradient, 128x128 tiles + XOR-swizzled LDS",
+        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 128x128 tiles",
         py::arg("dy"), py::arg("x"), py::arg("splitk"),
         py::arg("out_bf16") = false);
   m.def("wgrad_nt256", &wgrad_nt256,
-        "Split-K MFMA weight gradient, 256x256 tiles (8 waves)",
+        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 256x256 tiles",
         py::arg("dy"), py::arg("x"), py::arg("splitk"),
         py::arg("out_bf16") = false);
   m.def("col_reduce_dot", &col_reduce_dot,

@@ -4,8 +4,8 @@
 // Both operands are stored K-MAJOR (row-major with K innermost), which is
 // exactly what the mfma_f32_16x16x32_bf16 fragments want (8 consecutive k
 // per lane): staging into LDS is a LINEAR copy, no transpose — only the
-// fragment reads/writes use the combined XOR swizzle proven in
-// wgrad256.hip (same 256x256 tile / 8-wave / 4x8-fragment geometry).
+// fragment reads/writes use the XOR swizzle proven in wgrad.hip at
+// TILE=256 (same 256x256 tile / 8-wave / 4x8-fragment geometry).
 // K is tail-masked (K % 64 != 0 OK, K % 16 == 0 required); B rows are
 // masked so N % 256 != 0 works (the 432-wide dgrad shape).
 //
@@ -14,7 +14,7 @@
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -22,14 +22,7 @@ namespace {
 #define G_BN 256  // rows of B (= output cols) per tile
 #define G_BK 64
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_g;
-typedef __attribute__((ext_vector_type(4))) float f32x4_g;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_g;
-
-__device__ __forceinline__ int g_lds_off(int r, int k) {
-  int byte = r * 128 + k * 2;
-  return byte ^ (((r ^ (r >> 3)) & 7) << 4);
-}
 
 template <bool RELU>
 __global__ __launch_bounds__(512)
@@ -42,7 +35,7 @@ void gemm_bt_kernel(const unsigned short* __restrict__ A,
   const int tiles_m = static_cast<int>(M / G_BM);
   int tile_m, tile_n;
   if ((tiles_m & 7) == 0) {
-    // XCD-aware grouping (see wgrad256.hip): linear block b lands on
+    // XCD-aware grouping (see wgrad.hip): linear block b lands on
     // XCD b%8, so map the tiles_n column-tiles of each row-block to
     // indices sharing b%8 — they re-read the SAME 256 A rows and now
     // share them through one XCD's L2 instead of 4 different XCDs.
@@ -74,7 +67,7 @@ void gemm_bt_kernel(const unsigned short* __restrict__ A,
   const int st_k = (tid & 1) * 32;
   const bool b_row_ok = (n0 + st_r) < N;  // B rows masked for ragged N
 
-  f32x4_g acc[4][8];
+  mfma_f32x4 acc[4][8];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -113,9 +106,9 @@ void gemm_bt_kernel(const unsigned short* __restrict__ A,
   auto write_step = [&] {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      *reinterpret_cast<u16x8_g*>(aT + g_lds_off(st_r, st_k + c * 8)) =
+      *reinterpret_cast<u16x8_g*>(aT + lds_off_linear(st_r, st_k + c * 8)) =
           ra[c];
-      *reinterpret_cast<u16x8_g*>(bT + g_lds_off(st_r, st_k + c * 8)) =
+      *reinterpret_cast<u16x8_g*>(bT + lds_off_linear(st_r, st_k + c * 8)) =
           rb[c];
     }
   };
@@ -127,15 +120,15 @@ void gemm_bt_kernel(const unsigned short* __restrict__ A,
     if (k0 + G_BK < K) load_step(k0 + G_BK);  // in flight under MFMA
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
-      bf16x8_g a[4], b[8];
+      mfma_bf16x8 a[4], b[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        a[i] = *reinterpret_cast<const bf16x8_g*>(
-            aT + g_lds_off(wm + i * 16 + a_row, kh * 32 + a_k));
+        a[i] = *reinterpret_cast<const mfma_bf16x8*>(
+            aT + lds_off_linear(wm + i * 16 + a_row, kh * 32 + a_k));
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        b[j] = *reinterpret_cast<const bf16x8_g*>(
-            bT + g_lds_off(wn + j * 16 + a_row, kh * 32 + a_k));
+        b[j] = *reinterpret_cast<const mfma_bf16x8*>(
+            bT + lds_off_linear(wn + j * 16 + a_row, kh * 32 + a_k));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -1,158 +1,195 @@
-// Split-K MFMA weight-gradient kernel for MI355X (gfx950).
+// Split-K MFMA weight-gradient kernel for MI355X (gfx950), one template
+// over the output tile edge: 128 (v3) and 256 (v4).
 //
 // dW[N, M] = sum_b dy[b, n] * x[b, m]  with dy [B, N], x [B, M] bf16
 // row-major and B ~ 65536: the "reduction GEMM" shape hipBLASLt runs at
 // 140-380 TF on this chip (measured, scripts/micro_gemm.py) because its
-// split-K solutions are weak.  This kernel:
+// split-K solutions are weak.
 //
-//  * tiles the OUTPUT 64x64 per workgroup (4 waves, each a 32x32 quadrant
-//    of 2x2 mfma_f32_16x16x32_bf16 fragments),
-//  * splits K (the batch) across gridDim.y, each block reducing its
-//    contiguous K-chunk and writing an fp32 partial slab
-//    part[sk][N][M] (atomic-free, deterministic); the host sums slabs,
-//  * stages both operands TRANSPOSED into padded LDS ([n][k] / [m][k],
-//    k-stride padded to 40 elems so the 16-lane ds_read_b128 groups hit
-//    distinct banks) because BOTH mfma operand fragments want 8
-//    consecutive k per lane (A[i][k], B[k][j] with j = lane/16*8 + reg).
+// Ladder (B=65536, 1024x432 / 512x1024):
+//  * v2, 64x64 tiles, padded LDS, no prefetch (removed): 118-129 TF —
+//    redundant operand traffic (dy re-read tiles_m times, x re-read
+//    tiles_n times) plus LDS write conflicts bound it.
+//  * v3, TILE=128: halves that traffic (~1 GB for the 1024x432 layer);
+//    swizzled LDS, masked column edges (M need not divide the tile, so
+//    the model's 432-wide first layer is served directly), next-step
+//    global loads issued under the MFMA phase.  Still traffic-bound.
+//  * v4, TILE=256: halves it again (~0.5 GB), the regime where the
+//    B-sweep says the structure already matches hipBLASLt: 581/655 TF,
+//    633/738 TF with the slab-major grid below.
 //
-// Guide refs: §3 fragment layout (16x16x32_bf16: 8 bf16/lane in, 4 fp32
-// acc, C/D col=lane&15 row=(lane>>4)*4+reg), §2 LDS banking, G13.
+// Geometry: 2*TILE threads = TILE/32 waves in (TILE/64)(N) x 2(M)
+// quadrants, each wave 64 x TILE/2 = 4 x TILE/32 fragments (TILE=256:
+// 128 fp32 acc/lane — ~2 waves/SIMD, 1 block/CU with 64 KB LDS).  LDS
+// holds both operands TRANSPOSED as [n][64 k] / [m][64 k] rows of 128 B
+// under mfma_tile.h's combined swizzle: packed b64 transposed writes and
+// b128 fragment reads both conflict-light.  Each split-K block reduces
+// its contiguous k-chunk into an fp32 slab part[sk][N][M] (atomic-free,
+// deterministic); reduce_splitk sums the slabs.
+//
+// XCD-aware slab-major mapping: the dispatcher places linear block b on
+// XCD b % 8 (MI355X_MICROARCH "Workgroup dispatch").  With grid =
+// (splitk, tiles), linear id = slab + splitk*tile, so all tiles of one
+// k-slab land on XCD slab%8 and share their dy/x column reads through
+// that XCD's 4 MB L2 (the old (tiles, splitk) grid put every tile of a
+// slab on a DIFFERENT XCD — zero reuse; operand re-reads made the kernel
+// HBM-bound at ~5.6 TB/s).
+//
+// Double-buffering post-mortem (round 2): two LDS buffer pairs with one
+// barrier per k-step were tried twice at TILE=256 — runtime buffer select
+// (537 TF) and a 2x-unrolled constant-offset pipeline (544/580 TF) — and
+// BOTH lost to this single-buffered loop (581/655 TF measured).  At 2
+// waves/SIMD the two-barrier alternation keeps the MFMA and LDS-staging
+// phases of the co-resident waves interleaved; the "saved" barrier was
+// not the bottleneck.  Keep single-buffered.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
-#include "common.h"
+#include "mfma_tile.h"
+
+torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
 
 namespace {
 
-#define WG_BN 64
-#define WG_BM 64
 #define WG_BK 64
-// LDS k-stride (elements): 136 B rows -> transposed b64 writes and b128
-// fragment reads both bank-conflict-free (banking analysis in module doc)
-#define BKPAD 68
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_v;
-typedef __attribute__((ext_vector_type(4))) float f32x4_v;
 
 union U16x4 {
   unsigned short u[4];
   unsigned long long ll;
 };
 
-__global__ __launch_bounds__(256)
-void wgrad_nt_kernel(const unsigned short* __restrict__ dy,
-                     const unsigned short* __restrict__ x,
-                     float* __restrict__ part,
-                     int64_t B, int N, int M, int64_t chunk) {
-  const int tiles_m = M / WG_BM;
-  const int tile_n = blockIdx.x / tiles_m;
-  const int tile_m = blockIdx.x - tile_n * tiles_m;
-  const int n0 = tile_n * WG_BN;
-  const int m0 = tile_m * WG_BM;
-  const int64_t k_begin = (int64_t)blockIdx.y * chunk;
+template <int TILE>
+__global__ __launch_bounds__(2 * TILE)
+void wgrad_kernel(const unsigned short* __restrict__ dy,
+                  const unsigned short* __restrict__ x,
+                  float* __restrict__ part,
+                  int64_t B, int N, int M, int64_t chunk) {
+  constexpr int FN = 4;          // fragments per wave along N
+  constexpr int FM = TILE / 32;  // ... along M
+  constexpr int SC = TILE / 8;   // staging threads per k-row
+
+  const int tiles_m = (M + TILE - 1) / TILE;
+  const int tile_n = blockIdx.y / tiles_m;
+  const int tile_m = blockIdx.y - tile_n * tiles_m;
+  const int n0 = tile_n * TILE;
+  const int m0 = tile_m * TILE;
+  const int64_t k_begin = (int64_t)blockIdx.x * chunk;
   const int64_t k_end = min(B, k_begin + chunk);
 
-  __shared__ unsigned short lds[(WG_BN + WG_BM) * BKPAD];
-  unsigned short* dyT = lds;                       // [WG_BN][BKPAD]
-  unsigned short* xT = lds + WG_BN * BKPAD;        // [WG_BM][BKPAD]
+  __shared__ __attribute__((aligned(16))) unsigned char
+      lds_raw[2 * TILE * 128];
+  unsigned char* dyT = lds_raw;              // [TILE n][64 k] swizzled
+  unsigned char* xT = lds_raw + TILE * 128;  // [TILE m][64 k]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  const int wn = (wave >> 1) * 32;  // wave quadrant in the 64x64 tile
-  const int wm = (wave & 1) * 32;
+  const int wn = (wave >> 1) * 64;          // N-quadrants of 64
+  const int wm = (wave & 1) * (TILE / 2);   // 2 M-halves
 
-  // staging: threads 0-127 stage dy, 128-255 stage x.  Each thread loads
-  // 4 k-rows x 8 columns (4 x 16 B coalesced) and writes 8 packed
-  // ds_write_b64 (4 k-values per write) into the transposed image.
-  const int st_tile = tid >> 7;          // 0 = dy, 1 = x
-  const int st_t = tid & 127;
-  const int st_kg = (st_t >> 3) * 4;     // k base: 0,4,...,60
-  const int st_c = (st_t & 7) * 8;       // col base: 0,8,...,56
-  const unsigned short* st_src = st_tile ? x : dy;
-  unsigned short* st_dst = st_tile ? xT : dyT;
-  const int st_ld = st_tile ? M : N;
-  const int st_o0 = st_tile ? m0 : n0;
+  // staging map (per tile [64 k][TILE cols]): thread = 4 k-rows x 8 cols
+  // (4 x 16 B coalesced loads -> 8 packed b64 transposed LDS writes)
+  const int st_kg = (tid / SC) * 4;
+  const int st_c = (tid % SC) * 8;
 
-  f32x4_v acc[2][2];
+  mfma_f32x4 acc[FN][FM];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < FN; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < FM; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  const int a_row = lane & 15;        // fragment row (n) / col (m)
-  const int a_k = (lane >> 4) * 8;    // fragment k base
+  const int a_row = lane & 15;
+  const int a_k = (lane >> 4) * 8;
+  const bool m_edge = (m0 + TILE) > M;
+  const bool in0 = !m_edge || (m0 + st_c + 4) <= M;
+  const bool in1 = !m_edge || (m0 + st_c + 8) <= M;
 
-  for (int64_t k0 = k_begin; k0 < k_end; k0 += WG_BK) {
-    // ---- stage transposed (packed b64 writes) ---------------------------
-    {
+  // T14 split (guide G15): issue the NEXT step's global loads before this
+  // step's MFMA phase so HBM latency hides under compute; the register
+  // tile is written to LDS after the barrier.
+  bf16x4 rdy[4][2], rx[4][2];
+
+  auto load_step = [&](int64_t k0) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
       const unsigned short* src =
-          st_src + (k0 + st_kg) * (int64_t)st_ld + st_o0 + st_c;
-      bf16x4 r0a = reinterpret_cast<const bf16x4*>(src)[0];
-      bf16x4 r0b = reinterpret_cast<const bf16x4*>(src)[1];
-      src += st_ld;
-      bf16x4 r1a = reinterpret_cast<const bf16x4*>(src)[0];
-      bf16x4 r1b = reinterpret_cast<const bf16x4*>(src)[1];
-      src += st_ld;
-      bf16x4 r2a = reinterpret_cast<const bf16x4*>(src)[0];
-      bf16x4 r2b = reinterpret_cast<const bf16x4*>(src)[1];
-      src += st_ld;
-      bf16x4 r3a = reinterpret_cast<const bf16x4*>(src)[0];
-      bf16x4 r3b = reinterpret_cast<const bf16x4*>(src)[1];
+          dy + (k0 + st_kg + rr) * (int64_t)N + n0 + st_c;
+      rdy[rr][0] = reinterpret_cast<const bf16x4*>(src)[0];
+      rdy[rr][1] = reinterpret_cast<const bf16x4*>(src)[1];
+      const unsigned short* srcx =
+          x + (k0 + st_kg + rr) * (int64_t)M + m0 + st_c;
+      // real branches (EXEC-masked loads): an out-of-range lane must not
+      // issue the load at all (last row would read past the tensor)
+      rx[rr][0] = bf16x4{0, 0, 0, 0};
+      rx[rr][1] = bf16x4{0, 0, 0, 0};
+      if (in0) rx[rr][0] = reinterpret_cast<const bf16x4*>(srcx)[0];
+      if (in1) rx[rr][1] = reinterpret_cast<const bf16x4*>(srcx)[1];
+    }
+  };
+
+  auto write_step = [&] {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        U16x4 pa{{r0a[j], r1a[j], r2a[j], r3a[j]}};
+        U16x4 p{{rdy[0][h][j], rdy[1][h][j], rdy[2][h][j], rdy[3][h][j]}};
         *reinterpret_cast<unsigned long long*>(
-            st_dst + (st_c + j) * BKPAD + st_kg) = pa.ll;
-        U16x4 pb{{r0b[j], r1b[j], r2b[j], r3b[j]}};
+            dyT + lds_off(st_c + h * 4 + j, st_kg)) = p.ll;
+        U16x4 q{{rx[0][h][j], rx[1][h][j], rx[2][h][j], rx[3][h][j]}};
         *reinterpret_cast<unsigned long long*>(
-            st_dst + (st_c + 4 + j) * BKPAD + st_kg) = pb.ll;
+            xT + lds_off(st_c + h * 4 + j, st_kg)) = q.ll;
       }
-    }
+  };
+
+  load_step(k_begin);
+  for (int64_t k0 = k_begin; k0 < k_end; k0 += WG_BK) {
+    write_step();
     __syncthreads();
-    // ---- MFMA: 2x2 fragments x 2 k-halves -------------------------------
+    if (k0 + WG_BK < k_end)
+      load_step(k0 + WG_BK);  // in flight under the MFMA phase
+    // ---- MFMA: FN x FM fragments x 2 k-halves ---------------------------
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
-      bf16x8_v a[2], b[2];
+      mfma_bf16x8 a[FN], b[FM];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[i] = *reinterpret_cast<const bf16x8_v*>(
-            dyT + (wn + i * 16 + a_row) * BKPAD + kh * 32 + a_k);
-        b[i] = *reinterpret_cast<const bf16x8_v*>(
-            xT + (wm + i * 16 + a_row) * BKPAD + kh * 32 + a_k);
-      }
+      for (int i = 0; i < FN; ++i)
+        a[i] = *reinterpret_cast<const mfma_bf16x8*>(
+            dyT + lds_off(wn + i * 16 + a_row, kh * 32 + a_k));
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < FM; ++j)
+        b[j] = *reinterpret_cast<const mfma_bf16x8*>(
+            xT + lds_off(wm + j * 16 + a_row, kh * 32 + a_k));
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+      for (int i = 0; i < FN; ++i)
+#pragma unroll
+        for (int j = 0; j < FM; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               a[i], b[j], acc[i][j], 0, 0, 0);
     }
     __syncthreads();
   }
 
-  // ---- epilogue: fp32 partial slab --------------------------------------
-  float* out = part + (int64_t)blockIdx.y * N * M;
+  // ---- epilogue: fp32 partial slab (column-masked) ----------------------
+  float* out = part + (int64_t)blockIdx.x * N * M;
   const int c_col = lane & 15;
   const int c_row = (lane >> 4) * 4;
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < FN; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < FM; ++j) {
+      const int col = m0 + wm + j * 16 + c_col;
+      if (col >= M) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = n0 + wn + i * 16 + c_row + r;
-        const int col = m0 + wm + j * 16 + c_col;
         out[(int64_t)row * M + col] = acc[i][j][r];
       }
+    }
 }
 
-}  // namespace
-
-torch::Tensor reduce_splitk(torch::Tensor part, bool out_bf16);
-
-torch::Tensor wgrad_nt(torch::Tensor dy, torch::Tensor x,
-                       int64_t splitk, bool out_bf16) {
+template <int TILE>
+torch::Tensor wgrad_launch(torch::Tensor dy, torch::Tensor x,
+                           int64_t splitk, bool out_bf16) {
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2 &&
               dy.scalar_type() == torch::kBFloat16,
               "dy must be [B, N] bf16 contiguous");
@@ -163,25 +200,41 @@ torch::Tensor wgrad_nt(torch::Tensor dy, torch::Tensor x,
   const int N = static_cast<int>(dy.size(1));
   const int M = static_cast<int>(x.size(1));
   TORCH_CHECK(x.size(0) == B, "batch mismatch");
-  TORCH_CHECK(N % WG_BN == 0 && M % WG_BM == 0 && B % WG_BK == 0,
-              "wgrad_nt needs N, M % 64 == 0 and B % 64 == 0");
-  if (splitk <= 0) {
-    // enough blocks for ~2 per CU
-    const int tiles = (N / WG_BN) * (M / WG_BM);
-    splitk = std::max<int64_t>(1, 512 / std::max(1, tiles));
-  }
+  TORCH_CHECK(N % TILE == 0 && M % 8 == 0 && B % WG_BK == 0,
+              "wgrad_nt", TILE, " needs N % ", TILE,
+              " == 0, M % 8 == 0, B % 64 == 0");
+  const int tiles = (N / TILE) * ((M + TILE - 1) / TILE);
+  // block budget of one full residency wave: 256 8-wave blocks (1 per CU,
+  // 64 KB LDS) or 512 4-wave blocks.  sk sweep (scripts/micro_gemm.py):
+  // >32 splits exceed it and cliff; 32 is the measured optimum
+  constexpr int budget = TILE == 256 ? 256 : 512;
+  if (splitk <= 0)
+    splitk = std::min<int64_t>(
+        32, std::max<int64_t>(1, budget / std::max(1, tiles)));
   // chunk must be a multiple of WG_BK covering B
   int64_t chunk = ((B + splitk - 1) / splitk + WG_BK - 1) / WG_BK * WG_BK;
   splitk = (B + chunk - 1) / chunk;
   auto part = torch::empty({splitk, N, M},
                            dy.options().dtype(torch::kFloat32));
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  dim3 grid((N / WG_BN) * (M / WG_BM), splitk);
-  hipLaunchKernelGGL(wgrad_nt_kernel, grid, dim3(256), 0, stream,
+  dim3 grid(splitk, tiles);
+  hipLaunchKernelGGL(wgrad_kernel<TILE>, grid, dim3(2 * TILE), 0, stream,
                      reinterpret_cast<unsigned short*>(dy.data_ptr()),
                      reinterpret_cast<unsigned short*>(x.data_ptr()),
                      part.data_ptr<float>(), B, N, M, chunk);
   // fused split-K reduce (+bf16 cast when the consumer is a
   // bf16 parameter) — replaces torch reduce + .to elementwise
   return reduce_splitk(part, out_bf16);
+}
+
+}  // namespace
+
+torch::Tensor wgrad_nt128(torch::Tensor dy, torch::Tensor x,
+                          int64_t splitk, bool out_bf16) {
+  return wgrad_launch<128>(dy, x, splitk, out_bf16);
+}
+
+torch::Tensor wgrad_nt256(torch::Tensor dy, torch::Tensor x,
+                          int64_t splitk, bool out_bf16) {
+  return wgrad_launch<256>(dy, x, splitk, out_bf16);
 }
