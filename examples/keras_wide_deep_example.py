@@ -37,7 +37,10 @@ def experiment_fn(model_dir: str):
         model = KerasModel(FlatInputWideAndDeep(
             dense_dim=N_DENSE, table_sizes=[TABLE_ROWS] * N_SPARSE,
             embedding_dim=8, hidden=(64, 32)))
-        model.compile(optimizer="sgd", loss="binary_crossentropy")
+        # "auc": val_auc in fit's logs and in the evaluator task's log line,
+        # pooled over all validation batches by the streaming HIP kernel
+        model.compile(optimizer="sgd", loss="binary_crossentropy",
+                      metrics=["auc"])
 
         def input_data_fn():
             g = torch.Generator().manual_seed(1)

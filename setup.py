@@ -38,6 +38,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "wgrad.hip"),
         os.path.join(CSRC, "gemm_bt.hip"),
         os.path.join(CSRC, "lt_linear.hip"),
+        os.path.join(CSRC, "eval_metrics.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3"],

@@ -123,7 +123,12 @@ class Estimator:
 
     ``module_fn() -> nn.Module``; ``optimizer_fn(params) -> Optimizer``;
     ``loss_fn(outputs, labels) -> scalar``; optional
-    ``metrics_fn(outputs, labels) -> dict``.
+    ``metrics_fn(outputs, labels) -> dict``, averaged over the eval
+    batches; optional ``eval_metrics() -> accumulator`` with
+    ``update(outputs, labels)`` and ``result() -> dict``, a streaming
+    metric over the whole evaluation (e.g.
+    :class:`~tf_yarn_amd.estimator.eval_metrics.BinaryClassificationMetrics`),
+    built once per ``evaluate``; on a key clash it wins over ``metrics_fn``.
     ``input_fn() -> iterable of (features, labels)``.
     """
 
@@ -135,13 +140,15 @@ class Estimator:
                  config: Optional[RunConfig] = None,
                  metrics_fn: Optional[Callable] = None,
                  device: Optional[str] = None,
-                 train_step_fn: Optional[Callable] = None):
+                 train_step_fn: Optional[Callable] = None,
+                 eval_metrics: Optional[Callable] = None):
         self.config = config or RunConfig()
         self.model_dir = model_dir or self.config.model_dir
         self._module_fn = module_fn
         self._optimizer_fn = optimizer_fn
         self._loss_fn = loss_fn
         self._metrics_fn = metrics_fn
+        self._eval_metrics = eval_metrics
         self._train_step_fn = train_step_fn
         self.device = device or (
             "cuda" if torch.cuda.is_available() else "cpu")
@@ -279,6 +286,8 @@ class Estimator:
         total_loss = 0.0
         n_batches = 0
         metric_sums: Dict[str, float] = {}
+        streaming = (self._eval_metrics()
+                     if self._eval_metrics is not None else None)
         for batch in input_fn():
             features, labels = batch
             features = _to_device(features, self.device)
@@ -290,6 +299,8 @@ class Estimator:
             if self._metrics_fn is not None:
                 for k, v in self._metrics_fn(outputs, labels).items():
                     metric_sums[k] = metric_sums.get(k, 0.0) + float(v)
+            if streaming is not None:
+                streaming.update(outputs, labels)
             for h in hooks:
                 h.after_step(n_batches, float(loss), self)
             if steps is not None and n_batches >= steps:
@@ -300,6 +311,8 @@ class Estimator:
                   "global_step": self.global_step}
         for k, v in metric_sums.items():
             result[k] = v / max(1, n_batches)
+        if streaming is not None:
+            result.update(streaming.result())
         self._write_eval_events(result, name)
         module.train()
         return result

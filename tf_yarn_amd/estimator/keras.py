@@ -59,6 +59,17 @@ def _resolve_loss(loss) -> Callable:
     return table[loss]
 
 
+# compile(metrics=[...]) name (lower case) -> BinaryClassificationMetrics key
+_METRIC_KEYS = {
+    "auc": "auc",
+    "accuracy": "accuracy",
+    "precision": "precision",
+    "recall": "recall",
+    "auc_precision_recall": "auc_precision_recall",
+    "pr_auc": "auc_precision_recall",
+}
+
+
 class Callback:
     def on_epoch_end(self, epoch: int, logs: Dict,
                      model: "KerasModel") -> None: ...
@@ -104,6 +115,18 @@ class KerasModel:
                                             self.module.parameters())
         self.loss_fn = _resolve_loss(loss)
         self.metrics = list(metrics)
+        unknown = [m for m in self.metrics
+                   if str(m).lower() not in _METRIC_KEYS]
+        if unknown:
+            logger.warning("metrics %s are not computed; known: %s",
+                           unknown, sorted(_METRIC_KEYS))
+
+    def _metric_names(self) -> Dict[str, str]:
+        """Requested metric name in lower case (Keras reports ``"AUC"`` as
+        ``auc``) -> accumulator key, known names only; binary-classifier
+        metrics over the module's logits."""
+        return {str(m).lower(): _METRIC_KEYS[str(m).lower()]
+                for m in self.metrics if str(m).lower() in _METRIC_KEYS}
 
     def _batches(self, x, y, batch_size: int, shuffle: bool = True):
         n = x.shape[0]
@@ -146,8 +169,13 @@ class KerasModel:
             logs = {"loss": epoch_loss / max(1, n_b)}
             if validation_data is not None:
                 vx, vy = validation_data
-                logs["val_loss"] = self.evaluate(vx, vy,
-                                                 batch_size=batch_size)
+                if self._metric_names():
+                    val = self.evaluate(vx, vy, batch_size=batch_size,
+                                        return_dict=True)
+                    logs.update({f"val_{k}": v for k, v in val.items()})
+                else:
+                    logs["val_loss"] = self.evaluate(vx, vy,
+                                                     batch_size=batch_size)
             history["loss"].append(logs["loss"])
             if verbose:
                 logger.info("epoch %d: %s", epoch, logs)
@@ -168,16 +196,37 @@ class KerasModel:
             m.apply_sparse_updates(lr)
 
     @torch.no_grad()
-    def evaluate(self, x, y, batch_size: int = 32) -> float:
+    def evaluate(self, x, y, batch_size: int = 32,
+                 return_dict: bool = False):
+        """Mean batch loss; with ``return_dict=True``,
+        ``{"loss": ..., <metric>: ...}`` for the known names given to
+        ``compile(metrics=...)``, from one
+        :class:`BinaryClassificationMetrics` over all batches."""
         self.module.eval()
         x = torch.as_tensor(x).to(self._device)
         y = torch.as_tensor(y).to(self._device)
+        names = self._metric_names() if return_dict else {}
+        acc = None
+        if names:
+            from tf_yarn_amd.estimator.eval_metrics import \
+                BinaryClassificationMetrics
+            acc = BinaryClassificationMetrics()
         total, n_b = 0.0, 0
         for bx, by in self._batches(x, y, batch_size, shuffle=False):
-            total += float(self.loss_fn(self.module(bx), by))
+            out = self.module(bx)
+            total += float(self.loss_fn(out, by))
             n_b += 1
+            if acc is not None:
+                acc.update(out, by)
         self.module.train()
-        return total / max(1, n_b)
+        loss = total / max(1, n_b)
+        if not return_dict:
+            return loss
+        result = {"loss": loss}
+        if acc is not None:
+            values = acc.result()
+            result.update({name: values[key] for name, key in names.items()})
+        return result
 
     @torch.no_grad()
     def predict(self, x, batch_size: int = 256) -> torch.Tensor:
@@ -190,7 +239,8 @@ class KerasModel:
 
     def save(self, path: str) -> None:
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        torch.save({"module": self.module, "name": self.name}, path)
+        torch.save({"module": self.module, "name": self.name,
+                    "metrics": list(self.metrics)}, path)
 
     def save_weights(self, path: str) -> None:
         torch.save(self.module.state_dict(), path)
@@ -204,4 +254,6 @@ class KerasModel:
 def load_model(path: str) -> KerasModel:
     """Reference ``evaluator_task.py:65`` (tf.keras.models.load_model)."""
     state = torch.load(path, map_location="cpu", weights_only=False)
-    return KerasModel(state["module"], state.get("name", "model"))
+    model = KerasModel(state["module"], state.get("name", "model"))
+    model.metrics = list(state.get("metrics", ()))
+    return model

@@ -109,9 +109,14 @@ def keras_evaluate(experiment: KerasExperiment,
                 if experiment.validation_data_fn is not None:
                     vx, vy = experiment.validation_data_fn()
                     if model.loss_fn is None:
-                        model.compile(optimizer="sgd", loss="mse")
-                    loss = model.evaluate(vx, vy)
-                    logger.info("eval %s: loss=%.5f", name, loss)
+                        model.compile(optimizer="sgd", loss="mse",
+                                      metrics=model.metrics)
+                    if model.metrics:
+                        logger.info("eval %s: %s", name, model.evaluate(
+                            vx, vy, return_dict=True))
+                    else:
+                        loss = model.evaluate(vx, vy)
+                        logger.info("eval %s: loss=%.5f", name, loss)
                 evaluated.add(name)
             last_progress = time.time()
             if len(evaluated) >= epochs:

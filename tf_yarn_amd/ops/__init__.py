@@ -1301,3 +1301,98 @@ def linear_bias_relu_head(x: torch.Tensor, weight: torch.Tensor,
                           bias: torch.Tensor, w_head: torch.Tensor,
                           b_head: torch.Tensor) -> torch.Tensor:
     return LinearBiasReLUHeadFn.apply(x, weight, bias, w_head, b_head)
+
+
+# ---- streaming binary-classification eval state ----------------------------
+
+EVAL_BUCKETS = 4096  # score histogram bins, uniform in logit space [-16, 16)
+EVAL_SLOTS = 256     # the kernel's maximum grid: one fp64 sums slot per block
+
+
+class BinaryEvalState:
+    """Device state of the streaming binary eval metrics, all zero at start:
+
+    * ``hist`` int64 ``[2, EVAL_BUCKETS]``: histogram of the logits in
+      buckets of width 1/128 over ``[-16, 16)`` (both ends clamp), row 0 the
+      negatives, row 1 the positives;
+    * ``counts`` int64 ``[4]``: ``(n_valid, n_nan, tp, fp)``;
+    * ``sums`` float64 ``[EVAL_SLOTS, 2]``: per grid slot
+      ``(sum of loss, sum of sigmoid)``.
+
+    Adding two states elementwise is the state of the two streams
+    together."""
+
+    def __init__(self, device=None):
+        self.hist = torch.zeros(2, EVAL_BUCKETS, dtype=torch.int64,
+                                device=device)
+        self.counts = torch.zeros(4, dtype=torch.int64, device=device)
+        self.sums = torch.zeros(EVAL_SLOTS, 2, dtype=torch.float64,
+                                device=device)
+
+    def tensors(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.hist, self.counts, self.sums
+
+    def zero_(self) -> "BinaryEvalState":
+        for t in self.tensors():
+            t.zero_()
+        return self
+
+
+def _binary_eval_update_ref(z: torch.Tensor, y: torch.Tensor,
+                            state: BinaryEvalState) -> None:
+    """The spec of ``csrc/eval_metrics.hip`` in torch, every per-example
+    step in fp32; the sums go to slot 0."""
+    nan = torch.isnan(z) | torch.isnan(y)
+    n_nan = int(nan.sum())
+    z, y = z[~nan], y[~nan]
+    pos = y >= 0.5
+    hot = z > 0
+    # one rounding with or without FMA contraction (both constants are
+    # powers of two), so the kernel's bucket is this one to the bit
+    t = (z + 16.0) * 128.0
+    k = torch.floor(t).clamp_(0.0, EVAL_BUCKETS - 1.0).to(torch.int64)
+    state.hist[0] += torch.bincount(k[~pos], minlength=EVAL_BUCKETS)
+    state.hist[1] += torch.bincount(k[pos], minlength=EVAL_BUCKETS)
+    state.counts += torch.tensor(
+        [z.numel(), n_nan, int((pos & hot).sum()), int((~pos & hot).sum())],
+        dtype=torch.int64)
+    loss = z.clamp_min(0.0) - z * y + torch.log1p(torch.exp(-z.abs()))
+    sig = 1.0 / (1.0 + torch.exp(-z))
+    state.sums[0, 0] += loss.double().sum()
+    state.sums[0, 1] += sig.double().sum()
+
+
+def binary_eval_update(logits: torch.Tensor, labels: torch.Tensor,
+                       state: BinaryEvalState) -> None:
+    """Fold a batch of binary-classifier ``logits`` and 0/1 ``labels`` (any
+    shapes with equal element counts) into ``state``.  Per example, in
+    fp32 (bf16 logits widen exactly; other dtypes are cast)::
+
+        z or y NaN    -> n_nan += 1, nothing else
+        pos            = y >= 0.5
+        t              = (z + 16) * 128
+        k              = 0 if t < 0, 4095 if t >= 4096, else floor(t)
+        hist[pos][k]  += 1;  n_valid += 1
+        tp += pos and z > 0;  fp += not pos and z > 0
+        sums += (max(z,0) - z*y + log1p(exp(-|z|)),  1 / (1 + exp(-z)))
+
+    GPU: one HIP kernel (``csrc/eval_metrics.hip``), no host sync, and the
+    same batches in the same order give the same state bit for bit.  CPU:
+    the torch reference of the same arithmetic; ``hist`` and ``counts``
+    agree with the kernel exactly."""
+    z = logits.reshape(-1)
+    y = labels.reshape(-1)
+    if z.numel() != y.numel():
+        raise ValueError(f"{z.numel()} logits but {y.numel()} labels")
+    if y.dtype != torch.float32:
+        y = y.float()
+    if z.numel() == 0:
+        return
+    if _on_gpu(z, y, *state.tensors()):
+        _require_ext()
+        if z.dtype not in (torch.float32, torch.bfloat16):
+            z = z.float()
+        _C.binary_eval_update(z.contiguous(), y.contiguous(),
+                              *state.tensors())
+        return
+    _binary_eval_update_ref(z.float(), y, state)

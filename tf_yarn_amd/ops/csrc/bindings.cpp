@@ -132,6 +132,11 @@ void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale);
 torch::Tensor gemm_bt(torch::Tensor a, torch::Tensor b,
                       c10::optional<torch::Tensor> bias, bool relu);
 
+// eval_metrics.hip
+void binary_eval_update(torch::Tensor logits, torch::Tensor labels,
+                        torch::Tensor hist, torch::Tensor counts,
+                        torch::Tensor sums);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "tf_yarn_amd MI355X (gfx950) HIP kernels";
   m.def("fused_sgd", &fused_sgd, "Fused SGD(+momentum) step");
@@ -237,4 +242,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("convert_scaled", &convert_scaled, "Scaled bf16<->fp32 convert");
   m.def("gemm_bt", &gemm_bt,
         "C = A @ B^T (both K-major bf16) with fused bias+ReLU epilogue");
+  m.def("binary_eval_update", &binary_eval_update,
+        "Fold a batch of (logit, label) into the streaming binary eval "
+        "state: score histogram [2, 4096], counts (n_valid, n_nan, tp, fp), "
+        "per-slot fp64 (loss, sigmoid) sums [256, 2]",
+        py::arg("logits"), py::arg("labels"), py::arg("hist"),
+        py::arg("counts"), py::arg("sums"));
 }
