@@ -25,6 +25,13 @@ static inline int miyarn_grid(int64_t n_items) {
   return miyarn_grid_cap(n_items, MIYARN_MAX_BLOCKS);
 }
 
+// Vector accesses need their natural alignment: 16 B for f32x4 / bf16x8,
+// 8 B for bf16x4.  A view into a flat buffer at an odd element offset does
+// not have it; its launch must take the scalar loop for every element.
+static inline bool miyarn_aligned(const void* p, uintptr_t bytes) {
+  return reinterpret_cast<uintptr_t>(p) % bytes == 0;
+}
+
 // ---- bf16 <-> f32 ----------------------------------------------------------
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short u) {
@@ -33,7 +40,11 @@ __device__ __forceinline__ float bf16_to_f32(unsigned short u) {
   return v.f;
 }
 
+// A NaN becomes the quiet NaN 0x7fc0 (torch's): the rounding add below
+// would carry some NaN patterns into Inf (0x7f800001), -0.0 (0x7fffffff)
+// or +0.0 (0xffffffff).
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
+  if (f != f) return 0x7fc0;
   union { float f; unsigned int i; } v;
   v.f = f;
   unsigned int x = v.i;

@@ -175,8 +175,7 @@ __global__ void bias_relu_bwd_dbpart_kernel(
 // in column 2*cols (the last three are zero), so one reduce yields all
 // three vectors.
 __device__ __forceinline__ unsigned short bf16_mul_rne(float a, float b) {
-  const float p = a * b;
-  return p != p ? (unsigned short)0x7fc0 : f32_to_bf16(p);  // torch's NaN
+  return f32_to_bf16(a * b);  // a NaN comes out as 0x7fc0, torch's
 }
 
 template <bool HEAD, bool GRADS = false>
@@ -308,9 +307,9 @@ __global__ void bias_relu_bwd_kernel(
 
 __global__ void bf16_to_f32_kernel(const unsigned short* __restrict__ src,
                                    float* __restrict__ dst, int64_t n,
-                                   float scale) {
+                                   float scale, bool vec) {
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;  // !vec: all through the tail loop
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   for (int64_t i = tid; i < nvec; i += stride) {
     bf16x4 v = reinterpret_cast<const bf16x4*>(src)[i];
@@ -325,9 +324,9 @@ __global__ void bf16_to_f32_kernel(const unsigned short* __restrict__ src,
 
 __global__ void f32_to_bf16_kernel(const float* __restrict__ src,
                                    unsigned short* __restrict__ dst,
-                                   int64_t n, float scale) {
+                                   int64_t n, float scale, bool vec) {
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;  // !vec: all through the tail loop
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
@@ -757,18 +756,23 @@ void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale) {
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int64_t n = src.numel();
   int grid = miyarn_grid((n + 3) / 4);
+  // a view at an odd element offset is read and written by scalars
+  const bool f32_side = src.scalar_type() == torch::kFloat32;
+  const bool vec =
+      miyarn_aligned(src.data_ptr(), f32_side ? 16 : 8) &&
+      miyarn_aligned(dst.data_ptr(), f32_side ? 8 : 16);
   if (src.scalar_type() == torch::kBFloat16 &&
       dst.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream,
                        reinterpret_cast<unsigned short*>(src.data_ptr()),
-                       dst.data_ptr<float>(), n, (float)scale);
+                       dst.data_ptr<float>(), n, (float)scale, vec);
   } else if (src.scalar_type() == torch::kFloat32 &&
              dst.scalar_type() == torch::kBFloat16) {
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream, src.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(dst.data_ptr()),
-                       n, (float)scale);
+                       n, (float)scale, vec);
   } else {
     TORCH_CHECK(false, "convert_scaled supports bf16<->fp32 only");
   }

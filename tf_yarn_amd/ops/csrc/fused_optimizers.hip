@@ -8,9 +8,16 @@
 //
 // All kernels are memory-bound elementwise: 16 B/lane f32x4 vector accesses,
 // grid-stride, grid capped at 2048 blocks (guide Appendix B / G11/G13).
+//
+// The vector loop needs p, the state buffers and the bf16 copy at their
+// natural alignment (16 B, 8 B for the copy).  The host passes vec = false
+// for a call where one of them is not (a view into a flat buffer at an odd
+// element offset); nvec is then 0 and the scalar tail loop, which starts at
+// nvec * 4, takes every element.  g is read by scalars either way.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <initializer_list>
 #include "common.h"
 
 namespace {
@@ -25,10 +32,10 @@ __global__ void sgd_kernel(float* __restrict__ p,
                            const typename GIo::scalar_t* __restrict__ g,
                            float* __restrict__ mom,  // may be null
                            unsigned short* __restrict__ p_bf16,  // may be null
-                           int64_t n, SgdArgs a) {
+                           int64_t n, bool vec, SgdArgs a) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 mv;
@@ -70,34 +77,52 @@ __global__ void sgd_kernel(float* __restrict__ p,
   }
 }
 
+// omb1 / omb2 are 1 - beta rounded ONCE from the host's double: 1.f - beta
+// in fp32 is exact, but on the already rounded beta, and the rounding error
+// of beta = 0.99 is a 1e-6 relative error of 0.01, which put exp_avg_sq 8
+// ulps from a float64 evaluation where the CPU path is within 1.2.
 struct AdamArgs {
-  float lr, beta1, beta2, eps, weight_decay, bc1, bc2, scale;
+  float lr, beta1, beta2, omb1, omb2, eps, weight_decay, bc1, bc2, scale;
   bool adamw;
 };
+
+// One element of Adam / AdamW.  The vector loop and the scalar tail both go
+// through this function, and its multiply-adds are written out (fmaf, with
+// contraction off for the rest), so an element gets the same roundings
+// whichever loop takes it: a misaligned view, which runs the tail loop
+// only, gives the bits of an aligned one.
+__device__ __forceinline__ void adam_one(float g, float* p, float* m,
+                                         float* v, AdamArgs a) {
+#pragma clang fp contract(off)
+  float pv = *p;
+  float gv = g * a.scale;
+  if (a.adamw) pv = fmaf(-(a.lr * a.weight_decay), pv, pv);
+  else gv = fmaf(a.weight_decay, pv, gv);
+  const float mm = fmaf(a.beta1, *m, a.omb1 * gv);
+  const float vv = fmaf(a.beta2, *v, a.omb2 * gv * gv);
+  *m = mm;
+  *v = vv;
+  *p = pv - a.lr * (mm / a.bc1) / (sqrtf(vv / a.bc2) + a.eps);
+}
 
 template <typename GIo>
 __global__ void adam_kernel(float* __restrict__ p,
                             const typename GIo::scalar_t* __restrict__ g,
                             float* __restrict__ m_, float* __restrict__ v_,
                             unsigned short* __restrict__ p_bf16,
-                            int64_t n, AdamArgs a) {
+                            int64_t n, bool vec, AdamArgs a) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 mv = reinterpret_cast<f32x4*>(m_)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v_)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float gv = GIo::load(g, i * 4 + j) * a.scale;
-      if (a.adamw) pv[j] -= a.lr * a.weight_decay * pv[j];
-      else gv += a.weight_decay * pv[j];
-      mv[j] = a.beta1 * mv[j] + (1.f - a.beta1) * gv;
-      vv[j] = a.beta2 * vv[j] + (1.f - a.beta2) * gv * gv;
-      float mhat = mv[j] / a.bc1;
-      float vhat = vv[j] / a.bc2;
-      pv[j] -= a.lr * mhat / (sqrtf(vhat) + a.eps);
+      float pp = pv[j], mm = mv[j], v2 = vv[j];
+      adam_one(GIo::load(g, i * 4 + j), &pp, &mm, &v2, a);
+      pv[j] = pp; mv[j] = mm; vv[j] = v2;
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(m_)[i] = mv;
@@ -110,48 +135,47 @@ __global__ void adam_kernel(float* __restrict__ p,
     }
   }
   for (int64_t i = (nvec << 2) + tid; i < n; i += stride) {
-    float pv = p[i];
-    float gv = GIo::load(g, i) * a.scale;
-    if (a.adamw) pv -= a.lr * a.weight_decay * pv;
-    else gv += a.weight_decay * pv;
-    float m = a.beta1 * m_[i] + (1.f - a.beta1) * gv;
-    float v = a.beta2 * v_[i] + (1.f - a.beta2) * gv * gv;
-    m_[i] = m; v_[i] = v;
-    pv -= a.lr * (m / a.bc1) / (sqrtf(v / a.bc2) + a.eps);
-    p[i] = pv;
+    float pv = p[i], m = m_[i], v = v_[i];
+    adam_one(GIo::load(g, i), &pv, &m, &v, a);
+    p[i] = pv; m_[i] = m; v_[i] = v;
     if (p_bf16) p_bf16[i] = f32_to_bf16(pv);
   }
 }
 
 struct AdagradArgs { float lr, eps, weight_decay, scale; };
 
+// One element of Adagrad, shared by both loops (see adam_one).
+__device__ __forceinline__ void adagrad_one(float g, float* p, float* acc,
+                                            AdagradArgs a) {
+#pragma clang fp contract(off)
+  const float gv = fmaf(a.weight_decay, *p, g * a.scale);
+  const float s = fmaf(gv, gv, *acc);
+  *acc = s;
+  *p -= a.lr * gv / (sqrtf(s) + a.eps);
+}
+
 template <typename GIo>
 __global__ void adagrad_kernel(float* __restrict__ p,
                                const typename GIo::scalar_t* __restrict__ g,
                                float* __restrict__ acc,
-                               int64_t n, AdagradArgs a) {
+                               int64_t n, bool vec, AdagradArgs a) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 av = reinterpret_cast<f32x4*>(acc)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float gv = GIo::load(g, i * 4 + j) * a.scale;
-      gv += a.weight_decay * pv[j];
-      av[j] += gv * gv;
-      pv[j] -= a.lr * gv / (sqrtf(av[j]) + a.eps);
+      float pp = pv[j], aa = av[j];
+      adagrad_one(GIo::load(g, i * 4 + j), &pp, &aa, a);
+      pv[j] = pp; av[j] = aa;
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(acc)[i] = av;
   }
-  for (int64_t i = (nvec << 2) + tid; i < n; i += stride) {
-    float gv = GIo::load(g, i) * a.scale;
-    gv += a.weight_decay * p[i];
-    acc[i] += gv * gv;
-    p[i] -= a.lr * gv / (sqrtf(acc[i]) + a.eps);
-  }
+  for (int64_t i = (nvec << 2) + tid; i < n; i += stride)
+    adagrad_one(GIo::load(g, i), &p[i], &acc[i], a);
 }
 
 // Dense FTRL-proximal (TF Ftrl, learning_rate_power = -0.5, no beta, no L2
@@ -177,10 +201,10 @@ __global__ void ftrl_kernel(float* __restrict__ p,
                             const typename GIo::scalar_t* __restrict__ g,
                             float* __restrict__ accum,
                             float* __restrict__ linear,
-                            int64_t n, FtrlArgs a) {
+                            int64_t n, bool vec, FtrlArgs a) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 nv = reinterpret_cast<f32x4*>(accum)[i];
@@ -199,42 +223,46 @@ __global__ void ftrl_kernel(float* __restrict__ p,
     ftrl_one(GIo::load(g, i) * a.scale, &accum[i], &linear[i], &p[i], a);
 }
 
-struct AdadeltaArgs { float lr, rho, eps, weight_decay, scale; };
+// omr = 1 - rho from the host's double, as omb1 / omb2 above.
+struct AdadeltaArgs { float lr, rho, omr, eps, weight_decay, scale; };
+
+// One element of Adadelta, shared by both loops (see adam_one).
+__device__ __forceinline__ void adadelta_one(float g, float* p, float* sq,
+                                             float* acc_d, AdadeltaArgs a) {
+#pragma clang fp contract(off)
+  const float gv = fmaf(a.weight_decay, *p, g * a.scale);
+  const float s = fmaf(a.rho, *sq, a.omr * gv * gv);
+  const float dx = sqrtf(*acc_d + a.eps) / sqrtf(s + a.eps) * gv;
+  *sq = s;
+  *acc_d = fmaf(a.rho, *acc_d, a.omr * dx * dx);
+  *p = fmaf(-a.lr, dx, *p);
+}
 
 template <typename GIo>
 __global__ void adadelta_kernel(float* __restrict__ p,
                                 const typename GIo::scalar_t* __restrict__ g,
                                 float* __restrict__ sq,
                                 float* __restrict__ acc_d,
-                                int64_t n, AdadeltaArgs a) {
+                                int64_t n, bool vec, AdadeltaArgs a) {
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 sv = reinterpret_cast<f32x4*>(sq)[i];
     f32x4 dv = reinterpret_cast<f32x4*>(acc_d)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float gv = GIo::load(g, i * 4 + j) * a.scale;
-      gv += a.weight_decay * pv[j];
-      sv[j] = a.rho * sv[j] + (1.f - a.rho) * gv * gv;
-      float dx = sqrtf(dv[j] + a.eps) / sqrtf(sv[j] + a.eps) * gv;
-      dv[j] = a.rho * dv[j] + (1.f - a.rho) * dx * dx;
-      pv[j] -= a.lr * dx;
+      float pp = pv[j], ss = sv[j], dd = dv[j];
+      adadelta_one(GIo::load(g, i * 4 + j), &pp, &ss, &dd, a);
+      pv[j] = pp; sv[j] = ss; dv[j] = dd;
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(sq)[i] = sv;
     reinterpret_cast<f32x4*>(acc_d)[i] = dv;
   }
-  for (int64_t i = (nvec << 2) + tid; i < n; i += stride) {
-    float gv = GIo::load(g, i) * a.scale;
-    gv += a.weight_decay * p[i];
-    sq[i] = a.rho * sq[i] + (1.f - a.rho) * gv * gv;
-    float dx = sqrtf(acc_d[i] + a.eps) / sqrtf(sq[i] + a.eps) * gv;
-    acc_d[i] = a.rho * acc_d[i] + (1.f - a.rho) * dx * dx;
-    p[i] -= a.lr * dx;
-  }
+  for (int64_t i = (nvec << 2) + tid; i < n; i += stride)
+    adadelta_one(GIo::load(g, i), &p[i], &sq[i], &acc_d[i], a);
 }
 
 // ---- multi-tensor SGD ------------------------------------------------------
@@ -251,6 +279,7 @@ struct MtTensors {
   float* m[MT_MAX];           // nullptr if no momentum
   unsigned short* pb[MT_MAX]; // nullptr if no bf16 copy
   long numel[MT_MAX];
+  bool vec[MT_MAX];           // this tensor's pointers are vector-aligned
   int n;
 };
 
@@ -264,9 +293,10 @@ __global__ void sgd_mt_kernel(MtTensors t, SgdArgs a) {
       reinterpret_cast<const typename GIo::scalar_t*>(t.g[ti]);
   float* __restrict__ mom = t.m[ti];
   unsigned short* __restrict__ pb = t.pb[ti];
+  const bool vec = t.vec[ti];
   const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t nvec = n >> 2;
+  const int64_t nvec = vec ? n >> 2 : 0;
   for (int64_t i = tid; i < nvec; i += stride) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     f32x4 mv;
@@ -325,6 +355,15 @@ void check_grad(const torch::Tensor& g, int64_t n) {
   TORCH_CHECK(g.numel() == n, "grad numel mismatch");
 }
 
+// True when every vector-accessed pointer of a launch has its alignment:
+// f32 (p and the states; null = absent) 16 B, the bf16 copy 8 B.
+bool vec_aligned(std::initializer_list<const void*> f32,
+                 const void* bf16 = nullptr) {
+  for (const void* p : f32)
+    if (!miyarn_aligned(p, 16)) return false;
+  return miyarn_aligned(bf16, 8);
+}
+
 unsigned short* bf16_copy_ptr(const c10::optional<torch::Tensor>& t,
                               int64_t n) {
   if (!t.has_value()) return nullptr;
@@ -354,16 +393,17 @@ void fused_sgd(torch::Tensor param, torch::Tensor grad,
             (float)weight_decay, (float)grad_scale, nesterov, first_step};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = miyarn_grid((n + 3) / 4);
+  unsigned short* pb = bf16_copy_ptr(param_bf16, n);
+  const bool vec = vec_aligned({param.data_ptr(), mom}, pb);
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(sgd_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream, param.data_ptr<float>(),
-                       grad.data_ptr<float>(), mom,
-                       bf16_copy_ptr(param_bf16, n), n, a);
+                       grad.data_ptr<float>(), mom, pb, n, vec, a);
   } else {
     hipLaunchKernelGGL(sgd_kernel<Bf16Io>, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream, param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
-                       mom, bf16_copy_ptr(param_bf16, n), n, a);
+                       mom, pb, n, vec, a);
   }
 }
 
@@ -410,6 +450,7 @@ void fused_sgd_mt(std::vector<torch::Tensor> params,
             c10::optional<torch::Tensor>(params_bf16[base + i]), ne);
       }
       t.numel[i] = ne;
+      t.vec[i] = vec_aligned({t.p[i], t.m[i]}, t.pb[i]);
       max_numel = std::max(max_numel, ne);
     }
     dim3 grid(miyarn_grid((max_numel + 3) / 4), k);
@@ -434,26 +475,30 @@ void fused_adam(torch::Tensor param, torch::Tensor grad,
   check_flat_f32(exp_avg, "exp_avg", n);
   check_flat_f32(exp_avg_sq, "exp_avg_sq", n);
   check_grad(grad, n);
-  AdamArgs a{(float)lr, (float)beta1, (float)beta2, (float)eps,
+  AdamArgs a{(float)lr, (float)beta1, (float)beta2,
+             (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
              (float)weight_decay,
              (float)(1.0 - std::pow(beta1, (double)step)),
              (float)(1.0 - std::pow(beta2, (double)step)),
              (float)grad_scale, adamw};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = miyarn_grid((n + 3) / 4);
+  unsigned short* pb = bf16_copy_ptr(param_bf16, n);
+  const bool vec = vec_aligned(
+      {param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()}, pb);
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(adam_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream, param.data_ptr<float>(),
                        grad.data_ptr<float>(), exp_avg.data_ptr<float>(),
                        exp_avg_sq.data_ptr<float>(),
-                       bf16_copy_ptr(param_bf16, n), n, a);
+                       pb, n, vec, a);
   } else {
     hipLaunchKernelGGL(adam_kernel<Bf16Io>, dim3(grid), dim3(MIYARN_BLOCK), 0,
                        stream, param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
                        exp_avg.data_ptr<float>(),
                        exp_avg_sq.data_ptr<float>(),
-                       bf16_copy_ptr(param_bf16, n), n, a);
+                       pb, n, vec, a);
   }
 }
 
@@ -468,16 +513,17 @@ void fused_adagrad(torch::Tensor param, torch::Tensor grad,
                 (float)grad_scale};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = miyarn_grid((n + 3) / 4);
+  const bool vec = vec_aligned({param.data_ptr(), state_sum.data_ptr()});
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(adagrad_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK),
                        0, stream, param.data_ptr<float>(),
                        grad.data_ptr<float>(), state_sum.data_ptr<float>(),
-                       n, a);
+                       n, vec, a);
   } else {
     hipLaunchKernelGGL(adagrad_kernel<Bf16Io>, dim3(grid), dim3(MIYARN_BLOCK),
                        0, stream, param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
-                       state_sum.data_ptr<float>(), n, a);
+                       state_sum.data_ptr<float>(), n, vec, a);
   }
 }
 
@@ -494,17 +540,19 @@ void fused_ftrl(torch::Tensor param, torch::Tensor grad,
   FtrlArgs a{(float)lr, (float)l1, (float)l2, (float)grad_scale};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = miyarn_grid((n + 3) / 4);
+  const bool vec = vec_aligned(
+      {param.data_ptr(), accum.data_ptr(), linear.data_ptr()});
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(ftrl_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK),
                        0, stream, param.data_ptr<float>(),
                        grad.data_ptr<float>(), accum.data_ptr<float>(),
-                       linear.data_ptr<float>(), n, a);
+                       linear.data_ptr<float>(), n, vec, a);
   } else {
     hipLaunchKernelGGL(ftrl_kernel<Bf16Io>, dim3(grid), dim3(MIYARN_BLOCK),
                        0, stream, param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
                        accum.data_ptr<float>(), linear.data_ptr<float>(),
-                       n, a);
+                       n, vec, a);
   }
 }
 
@@ -517,21 +565,24 @@ void fused_adadelta(torch::Tensor param, torch::Tensor grad,
   check_flat_f32(square_avg, "square_avg", n);
   check_flat_f32(acc_delta, "acc_delta", n);
   check_grad(grad, n);
-  AdadeltaArgs a{(float)lr, (float)rho, (float)eps, (float)weight_decay,
+  AdadeltaArgs a{(float)lr, (float)rho, (float)(1.0 - rho), (float)eps,
+                 (float)weight_decay,
                  (float)grad_scale};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   int grid = miyarn_grid((n + 3) / 4);
+  const bool vec = vec_aligned(
+      {param.data_ptr(), square_avg.data_ptr(), acc_delta.data_ptr()});
   if (grad.scalar_type() == torch::kFloat32) {
     hipLaunchKernelGGL(adadelta_kernel<F32Io>, dim3(grid), dim3(MIYARN_BLOCK),
                        0, stream, param.data_ptr<float>(),
                        grad.data_ptr<float>(), square_avg.data_ptr<float>(),
-                       acc_delta.data_ptr<float>(), n, a);
+                       acc_delta.data_ptr<float>(), n, vec, a);
   } else {
     hipLaunchKernelGGL(adadelta_kernel<Bf16Io>, dim3(grid),
                        dim3(MIYARN_BLOCK), 0, stream,
                        param.data_ptr<float>(),
                        reinterpret_cast<unsigned short*>(grad.data_ptr()),
                        square_avg.data_ptr<float>(),
-                       acc_delta.data_ptr<float>(), n, a);
+                       acc_delta.data_ptr<float>(), n, vec, a);
   }
 }
