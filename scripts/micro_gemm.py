@@ -150,11 +150,75 @@ def custom_fwd():
               f"relerr {rel:.3e}")
 
 
+def _timed_windows(fn, iters=20, repeats=7):
+    """us per call: (median, min, max) over `repeats` device-event windows
+    of `iters` calls after a warm-up window (micro_tall_reduce.py's
+    convention); fn(i) gets the call number so it can rotate its inputs."""
+    import statistics
+    for i in range(iters):
+        fn(i)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for i in range(iters):
+            fn(i)
+        t1.record()
+        torch.cuda.synchronize()
+        out.append(t0.elapsed_time(t1) * 1e3 / iters)
+    return statistics.median(out), min(out), max(out)
+
+
+def dgrad_fused(sets=6, json_path=None):
+    """The two hidden-layer dgrads of the step with the ReLU backward of
+    the layer below, B = 65536: the library dgrad alone, the library dgrad
+    plus bias_relu_bwd_db (its reduce included), and dgrad_drelu.  Calls
+    rotate over `sets` input sets so operands come from HBM."""
+    import json
+    import tf_yarn_amd.ops._C as C
+    bf16 = torch.bfloat16
+    res = {"batch": B, "sets": sets}
+    for (k, n) in [(256, 512), (512, 1024)]:
+        w = (torch.randn(k, n, device="cuda") * 0.03).to(bf16)
+        dz = [torch.randn(B, k, device="cuda").to(bf16) for _ in range(sets)]
+        y = [torch.relu(torch.randn(B, n, device="cuda")).to(bf16)
+             for _ in range(sets)]
+        gf = 2 * B * k * n / 1e9
+        rows = [
+            ("lib dgrad", lambda i: dz[i % sets].matmul(w)),
+            ("lib dgrad + bias_relu_bwd_db",
+             lambda i: C.bias_relu_bwd_db(dz[i % sets].matmul(w),
+                                          y[i % sets], True)),
+            ("dgrad_drelu",
+             lambda i: C.dgrad_drelu(dz[i % sets], w, y[i % sets], True)),
+        ]
+        for name, fn in rows:
+            med, lo, hi = _timed_windows(fn)
+            res[f"{k}->{n} {name}"] = {
+                "median_us": round(med, 1), "min_us": round(lo, 1),
+                "max_us": round(hi, 1)}
+            print(f"[{k:>4}->{n:>4}] {name:30s} {med:7.1f} us "
+                  f"({lo:.1f} .. {hi:.1f})  {gf / med * 1e3:5.0f} TF",
+                  flush=True)
+        del dz, y
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)),
+                    exist_ok=True)
+        with open(json_path, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available()
     import sys as _sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    if "--bsweep" in _sys.argv:
+    if "--dgrad-fused" in _sys.argv:
+        dgrad_fused(json_path=_sys.argv[_sys.argv.index("--json") + 1]
+                    if "--json" in _sys.argv else None)
+    elif "--bsweep" in _sys.argv:
         wgrad_b_sweep()
     elif "--fwd" in _sys.argv:
         custom_fwd()

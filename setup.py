@@ -37,6 +37,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "elementwise.hip"),
         os.path.join(CSRC, "wgrad.hip"),
         os.path.join(CSRC, "gemm_bt.hip"),
+        os.path.join(CSRC, "dgrad_drelu.hip"),
         os.path.join(CSRC, "lt_linear.hip"),
         os.path.join(CSRC, "eval_metrics.hip"),
     ],

@@ -645,7 +645,9 @@ class WideAndDeep(nn.Module):
         layer and the head run as one autograd node whose backward never
         materialises the head's ``[B, width]`` input gradient
         (``ops.LinearBiasReLUHeadFn``; same kernels and bits otherwise).
-        MIYARN_FUSED_HEAD_BWD=0 keeps the two modules apart."""
+        MIYARN_FUSED_HEAD_BWD=0 keeps the two modules apart.  At a batch
+        that is a multiple of 256, a tower with a hidden layer whose dgrad
+        shape is routed to ``ops.dgrad_drelu`` runs as ``ops.MLPHeadFn``."""
         n = len(self.mlp)
         last = self.mlp[n - 1] if n else None
         head = self.head
@@ -659,6 +661,18 @@ class WideAndDeep(nn.Module):
                 and last.weight.shape[0] % 4 == 0
                 and ops.fused_head_bwd_enabled()):
             return head(self.mlp(deep_in))
+        # The whole tower as one node where a hidden layer's dgrad is
+        # routed to the kernel that applies the ReLU mask of the layer
+        # below in its epilogue (ops.MLPHeadFn; MIYARN_FUSED_DGRAD=0
+        # keeps the per-layer nodes).
+        if all(isinstance(m, FusedLinearReLU)
+               and m.weight.dtype == torch.bfloat16
+               and m.bias.dtype == torch.bfloat16 for m in self.mlp):
+            weights = [m.weight for m in self.mlp]
+            if ops.mlp_head_routed(deep_in, weights):
+                return ops.mlp_bias_relu_head(
+                    deep_in, weights, [m.bias for m in self.mlp],
+                    head.weight, head.bias)
         h = deep_in
         for i in range(n - 1):
             h = self.mlp[i](h)

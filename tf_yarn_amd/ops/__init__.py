@@ -1111,6 +1111,35 @@ def _custom_wgrad_kernel(dz: torch.Tensor, x: torch.Tensor):
     return None
 
 
+def _fused_dgrad_shape_routed(k: int, n: int) -> bool:
+    """Whether a hidden layer's dgrad of this shape (``dz_next [B, k]``,
+    weight ``[k, n]``) runs as ``_C.dgrad_drelu`` inside
+    :class:`MLPHeadFn`.  A shape is routed only if the fused kernel's
+    median lies below that of library dgrad + ``bias_relu_bwd_db`` by more
+    than the larger min..max spread of the two.  Measured
+    (``micro_gemm.py --dgrad-fused``, B=65536, median of 7 windows of 20
+    calls (min .. max), us; two boxes):
+
+    ===========  =========  =====================  =====================
+    k -> n       lib dgrad  lib + bias_relu_bwd    dgrad_drelu
+    ===========  =========  =====================  =====================
+    256 -> 512   32.1       79.8 (78.5 .. 80.5)    52.8 (51.9 .. 53.9)
+    256 -> 512   32.4       81.5 (80.4 .. 82.5)    54.9 (53.6 .. 57.0)
+    512 -> 1024  85.4       150.6 (149.1 .. 153.8)  133.3 (131.2 .. 135.0)
+    512 -> 1024  85.5       155.4 (155.2 .. 156.8)  137.2 (132.7 .. 141.9)
+    ===========  =========  =====================  =====================
+
+    Both pass: 27 us against a spread of 3.4, 17-18 us against 9.2.  The
+    larger shape passes only at the kernel's present 164 VGPRs (three
+    blocks per CU); at two blocks per CU it measured level with the
+    library pair (``profiles/r09_dgrad_drelu.md``).  Other shapes have not
+    been measured and stay on the library."""
+    return (k, n) in _FUSED_DGRAD_SHAPES
+
+
+_FUSED_DGRAD_SHAPES = frozenset({(256, 512), (512, 1024)})
+
+
 def _custom_fwd_ok(x: torch.Tensor, weight: torch.Tensor,
                    bias: torch.Tensor) -> bool:
     """True when gemm_bt should fuse the whole forward (GEMM + bias +
@@ -1301,6 +1330,153 @@ def linear_bias_relu_head(x: torch.Tensor, weight: torch.Tensor,
                           bias: torch.Tensor, w_head: torch.Tensor,
                           b_head: torch.Tensor) -> torch.Tensor:
     return LinearBiasReLUHeadFn.apply(x, weight, bias, w_head, b_head)
+
+
+# ---- dgrad + ReLU backward + dbias in one kernel; the tower as one node ----
+
+def fused_dgrad_enabled() -> bool:
+    """MIYARN_FUSED_DGRAD=0 keeps every hidden layer's dgrad on the library
+    GEMM followed by ``bias_relu_bwd_db``, and the deep tower on one
+    autograd node per layer.  Read per call."""
+    return _env_switch_on("MIYARN_FUSED_DGRAD")
+
+
+def _dgrad_drelu_kernel_ok(dz_next: torch.Tensor, weight: torch.Tensor,
+                           y: torch.Tensor) -> bool:
+    """The preconditions of ``_C.dgrad_drelu`` (``gemm_bt``'s)."""
+    if not (HAVE_EXT and dz_next.is_cuda and weight.is_cuda and y.is_cuda):
+        return False
+    if not (dz_next.dtype == weight.dtype == y.dtype == torch.bfloat16):
+        return False
+    if not (dz_next.dim() == 2 and weight.dim() == 2 and y.dim() == 2):
+        return False
+    m, k = dz_next.shape
+    n = weight.shape[1]
+    return (weight.shape[0] == k and tuple(y.shape) == (m, n) and m > 0
+            and m % 256 == 0 and k % 16 == 0 and n % 16 == 0)
+
+
+def dgrad_drelu(dz_next: torch.Tensor, weight: torch.Tensor,
+                y: torch.Tensor):
+    """``(dz, dbias)`` of the layer below a hidden layer, from that layer's
+    ``dz_next [B, K]``, its weight as stored ``[K, N]`` and the lower
+    layer's ReLU output ``y [B, N]``::
+
+        dz    = where(y > 0, dz_next @ weight, 0)     rounded to y's dtype
+        dbias = dz.sum(0)                             of the rounded values
+
+    bf16 GPU operands with ``B % 256 == 0`` and ``K``, ``N`` multiples of 16
+    run as ONE MFMA kernel (``csrc/dgrad_drelu.hip``) whose epilogue applies
+    the mask and forms the column sums, so ``dz_next @ weight`` never
+    reaches memory.  Everything else composes the library GEMM and
+    :func:`bias_relu_bwd_db`'s kernel, or the plain ops on the CPU."""
+    if _dgrad_drelu_kernel_ok(dz_next, weight, y):
+        dz, dbias = _C.dgrad_drelu(dz_next.contiguous(),
+                                   weight.contiguous(), y.contiguous(),
+                                   True)
+        return dz, dbias
+    return _relu_bwd_db(dz_next.matmul(weight), y)
+
+
+def _relu_bwd_db(dy: torch.Tensor, y: torch.Tensor):
+    """``(dz, dbias)`` from a layer's output gradient, exactly as
+    :class:`LinearBiasReLU`'s backward computes them."""
+    dy = dy.contiguous()
+    if dy.is_cuda and HAVE_EXT and y.size(-1) % 4 == 0 \
+            and y.size(-1) <= 8192:
+        dz, dbias = _C.bias_relu_bwd_db(
+            dy, y.contiguous(), dy.dtype == torch.bfloat16)
+        if dbias.dtype != dy.dtype:
+            dbias = dbias.to(dy.dtype)
+        return dz, dbias
+    dz = bias_relu_bwd(dy, y)
+    return dz, dz.sum(dim=tuple(range(dz.dim() - 1)))
+
+
+class MLPHeadFn(torch.autograd.Function):
+    """The whole deep tower, ``n`` bias+ReLU layers and the single-logit
+    head, as ONE autograd node.  The ReLU mask of layer ``l`` needs
+    ``y_l``, which per-layer nodes hand to layer ``l``'s backward; with one
+    node, layer ``l+1``'s dgrad can apply it in its own epilogue
+    (:func:`dgrad_drelu`).  Forward runs the per-layer nodes' kernels and
+    saves the tensors they save; backward computes what they compute,
+    kernel for kernel, except on the layers :func:`_fused_dgrad_shape_routed`
+    sends to the fused kernel.
+
+    ``apply(x, w_head, b_head, *weights, *biases)``."""
+
+    @staticmethod
+    def forward(ctx, x, w_head, b_head, *wb):
+        n = len(wb) // 2
+        weights, biases = wb[:n], wb[n:]
+        ys = []
+        h = x
+        for w, b in zip(weights, biases):
+            h = _linear_bias_relu_fwd(h, w, b)
+            ys.append(h)
+        ctx.n_layers = n
+        ctx.save_for_backward(x, w_head, *weights, *ys)
+        if _on_gpu(h, w_head) and h.size(1) % 4 == 0 \
+                and h.size(1) <= 512 and b_head.numel() == 1:
+            _require_ext()
+            return _C.row_dot(h.contiguous(), w_head.contiguous(),
+                              b_head.reshape(1))
+        return h @ w_head + b_head
+
+    @staticmethod
+    def backward(ctx, dl):
+        n = ctx.n_layers
+        saved = ctx.saved_tensors
+        x, w_head = saved[0], saved[1]
+        weights, ys = saved[2:2 + n], saved[2 + n:]
+        dl = dl.contiguous()
+        dw_head = db_head = None
+        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] \
+                and _on_gpu(dl, ys[-1]) and fused_head_grads_enabled():
+            dz, dbias, dw_head, db_head = head_relu_bwd_grads(
+                dl, w_head, ys[-1])
+        else:
+            if ctx.needs_input_grad[1]:
+                dw_head = col_reduce_dot(ys[-1], dl).to(w_head.dtype)
+            if ctx.needs_input_grad[2]:
+                db_head = dl.sum().reshape(1).to(w_head.dtype)
+            dz, dbias = head_relu_bwd_db(dl, w_head, ys[-1])
+        dws = [None] * n
+        dbs = [None] * n
+        fused = fused_dgrad_enabled()
+        for l in range(n - 1, 0, -1):
+            w, y_below = weights[l], ys[l - 1]
+            dws[l] = _linear_wgrad(dz, y_below, w)
+            dbs[l] = dbias
+            if fused and _fused_dgrad_shape_routed(*w.shape) \
+                    and _dgrad_drelu_kernel_ok(dz, w, y_below):
+                dz, dbias = dgrad_drelu(dz, w, y_below)
+            else:
+                dz, dbias = _relu_bwd_db(dz.matmul(w), y_below)
+        dx = dz.matmul(weights[0]) if ctx.needs_input_grad[0] else None
+        dws[0] = _linear_wgrad(dz, x, weights[0])
+        dbs[0] = dbias
+        return (dx, dw_head, db_head, *dws, *dbs)
+
+
+def mlp_bias_relu_head(x: torch.Tensor, weights, biases,
+                       w_head: torch.Tensor,
+                       b_head: torch.Tensor) -> torch.Tensor:
+    """``head(relu(... relu(x @ W_0.T + b_0) ...))`` for a single-logit
+    head, as one autograd node (:class:`MLPHeadFn`)."""
+    return MLPHeadFn.apply(x, w_head, b_head, *weights, *biases)
+
+
+def mlp_head_routed(x: torch.Tensor, weights) -> bool:
+    """True when :class:`MLPHeadFn` would send at least one hidden layer's
+    dgrad of this tower to the fused kernel: the batch is a multiple of
+    256, the switch is on and some layer above the first has a routed
+    shape."""
+    if not (fused_dgrad_enabled() and x.dim() == 2 and x.size(0) > 0
+            and x.size(0) % 256 == 0):
+        return False
+    return any(_fused_dgrad_shape_routed(*w.shape) and w.shape[0] % 16 == 0
+               and w.shape[1] % 16 == 0 for w in weights[1:])
 
 
 # ---- streaming binary-classification eval state ----------------------------

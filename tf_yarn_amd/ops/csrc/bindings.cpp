@@ -132,6 +132,10 @@ void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale);
 torch::Tensor gemm_bt(torch::Tensor a, torch::Tensor b,
                       c10::optional<torch::Tensor> bias, bool relu);
 
+// dgrad_drelu.hip
+std::vector<torch::Tensor> dgrad_drelu(torch::Tensor dz_next, torch::Tensor w,
+                                       torch::Tensor y, bool dbias_bf16);
+
 // eval_metrics.hip
 void binary_eval_update(torch::Tensor logits, torch::Tensor labels,
                         torch::Tensor hist, torch::Tensor counts,
@@ -242,6 +246,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("convert_scaled", &convert_scaled, "Scaled bf16<->fp32 convert");
   m.def("gemm_bt", &gemm_bt,
         "C = A @ B^T (both K-major bf16) with fused bias+ReLU epilogue");
+  m.def("dgrad_drelu", &dgrad_drelu,
+        "Hidden-layer dgrad dz_next @ w with the ReLU backward of the layer "
+        "below and its dbias in the epilogue (returns [dz, dbias])",
+        py::arg("dz_next"), py::arg("w"), py::arg("y"),
+        py::arg("dbias_bf16") = false);
   m.def("binary_eval_update", &binary_eval_update,
         "Fold a batch of (logit, label) into the streaming binary eval "
         "state: score histogram [2, 4096], counts (n_valid, n_nan, tp, fp), "
