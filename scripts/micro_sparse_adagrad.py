@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the stateful sparse apply (Adagrad, FTRL) at the
-bench shape (b=65536, 26 features x 1M rows, dim 16 deep + dim 1 wide,
-bf16 grads).  --rule picks the update rule: adagrad (both tables), ftrl
+"""Micro-benchmark of the stateful sparse apply (Adagrad, FTRL, lazy Adam)
+at the bench shape (b=65536, 26 features x 1M rows, dim 16 deep + dim 1
+wide, bf16 grads).  --rule picks the update rule: adagrad (both tables), ftrl
 (both tables), adagrad+ftrl (deep Adagrad, wide FTRL: the wide-and-deep
 recipe), rowwise+adagrad / rowwise+ftrl (row-wise Adagrad on the deep
 table, one state value per row, with that wide rule) or rowwise (the deep
-table alone, no wide companion).  The three row-wise settings also time
-pass 2 of their element-wise counterpart on the same tables in the same
-process, before and after a second row-wise window.
+table alone, no wide companion), lazy_adam (both tables) or lazy_adam_ftrl
+(deep lazy Adam, wide FTRL).  A lazy-Adam side is built anew for every
+call, with the next step count, as the model builds it.  The three row-wise
+settings also time pass 2 of their element-wise counterpart on the same
+tables in the same process, before and after a second row-wise window.
 
 Timed, on identical inputs:
   * the fused deep+wide update: pass 1 (atomic accumulate, the existing
@@ -39,9 +41,13 @@ F = 26
 DIM = 16
 LR, EPS = 0.01, 1e-10
 L1, L2 = 0.001, 0.001  # FTRL
+BETA1, BETA2 = 0.9, 0.999  # lazy Adam
 # --rule's names -> the ops' rule names
 RULE_NAMES = {"adagrad": "adagrad", "ftrl": "ftrl",
-              "rowwise": "rowwise_adagrad"}
+              "rowwise": "rowwise_adagrad", "lazy_adam": "lazy_adam"}
+# --rule settings whose name is not "deep+wide"
+RULE_SETTINGS = {"lazy_adam": ("lazy_adam", "lazy_adam"),
+                 "lazy_adam_ftrl": ("lazy_adam", "ftrl")}
 
 
 def timed(fn, iters, repeats):
@@ -89,6 +95,17 @@ def _baseline_rows(rule, table, states, uniq, g):
         table.index_copy_(0, uniq, w.addcdiv_(g, s.sqrt_().add_(EPS),
                                               value=-LR))
         return
+    if rule == "lazy_adam":
+        # the rule of ops._lazy_adam_rows_ref at a fixed step count
+        step_size = LR * (1 - BETA2 ** 10) ** 0.5 / (1 - BETA1 ** 10)
+        m = states[0].index_select(0, uniq)
+        v = states[1].index_select(0, uniq)
+        m = m + (1 - BETA1) * (g - m)
+        v = v + (1 - BETA2) * (g * g - v)
+        states[0].index_copy_(0, uniq, m)
+        states[1].index_copy_(0, uniq, v)
+        table.index_copy_(0, uniq, w - (step_size * m) / (v.sqrt() + EPS))
+        return
     n, z, w = ops._ftrl_rule(g, states[0].index_select(0, uniq),
                              states[1].index_select(0, uniq), w, LR, L1, L2)
     states[0].index_copy_(0, uniq, n)
@@ -115,6 +132,8 @@ def make_states(rule, table):
         return [torch.zeros(table.shape[0], device=table.device)]
     if rule == "adagrad":
         return [torch.zeros_like(table)]
+    if rule == "lazy_adam":
+        return [torch.zeros_like(table), torch.zeros_like(table)]
     return [torch.full_like(table, 0.1), torch.zeros_like(table)]
 
 
@@ -126,14 +145,15 @@ def main():
                     help="Zipf exponent (> 1) for the ids; 0 = uniform")
     ap.add_argument("--rule", default="adagrad",
                     choices=["adagrad", "ftrl", "adagrad+ftrl", "rowwise",
-                             "rowwise+adagrad", "rowwise+ftrl"],
+                             "rowwise+adagrad", "rowwise+ftrl", "lazy_adam",
+                             "lazy_adam_ftrl"],
                     help="update rule of the deep[+wide] table")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
-    rules = tuple(args.rule.split("+"))
+    rules = RULE_SETTINGS.get(args.rule) or tuple(args.rule.split("+"))
     if len(rules) == 1 and args.rule != "rowwise":
         rules *= 2
     pair = len(rules) == 2
@@ -164,20 +184,36 @@ def main():
         print(f"{name:32s} {med:8.1f} us  ({lo:.1f} .. {hi:.1f})",
               flush=True)
 
+    steps = {}  # id(table) -> updates applied, for the lazy-Adam sides
+
+    def adam_tail(rule, tbl):
+        """(beta1, beta2, next step count) behind a lazy-Adam side."""
+        if rule != "lazy_adam":
+            return ()
+        steps[id(tbl)] = steps.get(id(tbl), 0) + 1
+        return (BETA1, BETA2, steps[id(tbl)])
+
     def side(rule, tbl, sts, g):
         """One table's side under `rule`, this script's name for it."""
         return ops.SparseSide(RULE_NAMES[rule], tbl, tuple(sts), g, LR, EPS,
-                              L1, L2)
+                              L1, L2, *adam_tail(rule, tbl))
 
     def pass2_of(deep_rule, deep_states):
         """Pass 2 alone, straight on the C++ entry: sides without
         gradients, the wide companion whenever --rule has one."""
         def c_side(rule, tbl, sts, acc):
             return (RULE_NAMES[rule], tbl, list(sts), acc, None, LR, EPS,
-                    L1, L2)
-        d = c_side(deep_rule, table, deep_states, ws.acc)
-        w = c_side(rules[1], wide, wide_states, ws.wide_acc) if pair \
-            else None
+                    L1, L2) + adam_tail(rule, tbl)
+
+        def sides():
+            return (c_side(deep_rule, table, deep_states, ws.acc),
+                    c_side(rules[1], wide, wide_states, ws.wide_acc)
+                    if pair else None)
+        if "lazy_adam" in (deep_rule,) + rules[1:]:
+            # the step count differs from call to call
+            return lambda: C.emb_bwd_sparse(*sides(), ws.stamp, ids,
+                                            ws.next_epoch(), 1.0)
+        d, w = sides()
         return lambda: C.emb_bwd_sparse(d, w, ws.stamp, ids,
                                         ws.next_epoch(), 1.0)
 

@@ -347,6 +347,9 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
     ``sparse_optimizer="rowwise_adagrad"`` keeps ``state_sum_row``, one
     value per owned deep row, and defaults the wide table to
     ``"adagrad"``; it is not a rule for the dim-1 wide table.
+    ``"lazy_adam"`` keeps ``adam_exp_avg`` + ``adam_exp_avg_sq`` +
+    ``adam_step`` / ``wide_adam_...`` (betas: ``sparse_betas``; each table
+    counts its own updates).
     ``sparse_l1`` / ``sparse_l2`` regularise FTRL, ``wide_sparse_lr``
     fixes the wide table's lr.  The binned scatter and its forward-time
     permutation prefetch are SGD-only and run only when both tables are
@@ -361,7 +364,8 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
                  sparse_initial_accumulator: float = 0.0,
                  wide_sparse_optimizer: Optional[str] = None,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 wide_sparse_lr: Optional[float] = None):
+                 wide_sparse_lr: Optional[float] = None,
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
         super().__init__()
         import math
         self.F = len(table_sizes)
@@ -393,7 +397,7 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
             {"": (self.weight, sparse_optimizer),
              "wide_": (self.wide_weight, wide_sparse_optimizer)},
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
-            wide_sparse_lr=wide_sparse_lr)
+            wide_sparse_lr=wide_sparse_lr, sparse_betas=sparse_betas)
         offs = torch.tensor(
             [0] + list(torch.cumsum(torch.tensor(own_sizes), 0)[:-1]),
             dtype=torch.int64)
@@ -559,8 +563,8 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
 
     def _apply_pending_stateful(self, lr: float) -> None:
         """Owner-local update when at least one table has a stateful rule
-        (Adagrad, FTRL, row-wise Adagrad).  Deep and wide sink entries that
-        share their flat ids go to ``ops.emb_bwd_sparse`` as one pair when
+        (Adagrad, FTRL, lazy Adam, row-wise Adagrad).  Deep and wide sink
+        entries that share their flat ids go to ``ops.emb_bwd_sparse`` as one pair when
         both rules are stateful: it runs the pair's fused deep+wide kernel
         where there is one (ids read once per pass, one claim per row for
         both tables) and the two single-table updates otherwise.  An SGD

@@ -44,6 +44,10 @@ DEFAULT_TABLE_SIZES = [1_000_000] * CRITEO_SPARSE
 SPARSE_OPTIMIZERS = ("sgd", "adagrad", "ftrl")
 # tables with dim > 1 also take the rule with one state value per row
 DEEP_SPARSE_OPTIMIZERS = SPARSE_OPTIMIZERS + ("rowwise_adagrad",)
+# the rules with a per-table step count, accepted for any table, dim 1
+# included; kept apart from the two tuples above, which name the rules from
+# before lazy Adam
+ADAM_SPARSE_OPTIMIZERS = ("lazy_adam",)
 
 
 def _check_sparse_rule(name: str, value: str, dim: int = 1) -> str:
@@ -52,8 +56,9 @@ def _check_sparse_rule(name: str, value: str, dim: int = 1) -> str:
         raise ValueError(
             f"{name}={value!r}: a dim-1 table's row-wise rule is "
             f"\"adagrad\" (one state value per row already); pick one of "
-            f"{SPARSE_OPTIMIZERS}")
-    allowed = DEEP_SPARSE_OPTIMIZERS if dim > 1 else SPARSE_OPTIMIZERS
+            f"{SPARSE_OPTIMIZERS + ADAM_SPARSE_OPTIMIZERS}")
+    allowed = (DEEP_SPARSE_OPTIMIZERS if dim > 1 else SPARSE_OPTIMIZERS) \
+        + ADAM_SPARSE_OPTIMIZERS
     if value not in allowed:
         raise ValueError(
             f"{name} must be one of {allowed}, got {value!r}")
@@ -73,7 +78,34 @@ _RULE_STATES = {
     "adagrad": (_State("state_sum"),),
     "rowwise_adagrad": (_State("state_sum_row", per_row=True),),
     "ftrl": (_State("ftrl_accum"), _State("ftrl_linear", from_init=False)),
+    "lazy_adam": (_State("adam_exp_avg", from_init=False),
+                  _State("adam_exp_avg_sq", from_init=False)),
 }
+
+# the persistent int64 scalar a lazy-Adam table's step count is saved in
+_ADAM_STEP = "adam_step"
+
+
+def _adam_steps_to_buffers(module, prefix, keep_vars) -> None:
+    """``state_dict`` pre-hook: write the step counts (Python ints, the
+    authority) into their buffers.  A fill, so nothing waits for the
+    device."""
+    for p, t in module._adam_steps.items():
+        getattr(module, p + _ADAM_STEP).fill_(t)
+
+
+def _adam_steps_before_load(module, state_dict, prefix, *unused) -> None:
+    """``load_state_dict`` pre-hook: bring the buffers up to date first, so
+    a state dict WITHOUT a step key (``strict=False``) reads back the count
+    the module already has, not the one of its last ``state_dict()``."""
+    _adam_steps_to_buffers(module, prefix, False)
+
+
+def _adam_steps_from_buffers(module, incompatible_keys) -> None:
+    """``load_state_dict`` post-hook: the one place a step count is read
+    back from the device (one ``.item()`` per lazy-Adam table per load)."""
+    for p in module._adam_steps:
+        module._adam_steps[p] = int(getattr(module, p + _ADAM_STEP).item())
 
 
 def _default_wide_rule(sparse_optimizer: str) -> str:
@@ -103,6 +135,18 @@ class SparseOptimizerMixin:
       ONE persistent fp32 value per row (shape ``[rows]``, filled with
       ``sparse_initial_accumulator``) and no ``state_sum``: ``rows`` floats
       of state instead of ``rows x dim``;
+    * ``"lazy_adam"`` (any table): ``<p>adam_exp_avg`` and
+      ``<p>adam_exp_avg_sq``, persistent fp32 buffers shaped like the table
+      that start at 0 whatever ``sparse_initial_accumulator`` is, and the
+      table's step count.  The count is a Python int on the module (no
+      apply ever waits for the device to learn it) that advances once per
+      applied update of that table; checkpoints carry it as the persistent
+      int64 scalar buffer ``<p>adam_step``, which is refreshed from the int
+      whenever ``state_dict()`` is taken and read back (one ``.item()``)
+      when a state dict is loaded.  Between those two moments the buffer
+      may be stale: read ``adam_step_count(<p>)``.  ``sparse_betas`` are
+      its betas; ``sparse_eps`` is shared with the Adagrad rules, whose
+      default (1e-10) it keeps: pass ``sparse_eps=1e-8`` for Adam's usual;
     * a non-persistent accumulator + int32 row stamp, allocated on the
       first apply (:class:`tf_yarn_amd.ops.SparseWorkspace`, shared by
       the pair whatever their rules).
@@ -116,7 +160,9 @@ class SparseOptimizerMixin:
                                sparse_initial_accumulator: float,
                                tables: dict, sparse_l1: float = 0.0,
                                sparse_l2: float = 0.0,
-                               wide_sparse_lr: Optional[float] = None
+                               wide_sparse_lr: Optional[float] = None,
+                               sparse_betas: Tuple[float, float] = (0.9,
+                                                                    0.999)
                                ) -> None:
         """``tables``: state-name prefix -> (table parameter, rule), deep
         table first; the first stateful entry owns the row stamp."""
@@ -129,6 +175,11 @@ class SparseOptimizerMixin:
         if wide_sparse_lr is not None and not wide_sparse_lr > 0:
             raise ValueError(
                 f"wide_sparse_lr must be > 0, got {wide_sparse_lr!r}")
+        beta1, beta2 = (float(b) for b in sparse_betas)
+        if not (0 <= beta1 < 1 and 0 <= beta2 < 1):
+            raise ValueError("sparse_betas must both be in [0, 1), got "
+                             f"{sparse_betas!r}")
+        self.sparse_betas = (beta1, beta2)
         self.sparse_eps = float(sparse_eps)
         self.sparse_l1 = float(sparse_l1)
         self.sparse_l2 = float(sparse_l2)
@@ -149,6 +200,20 @@ class SparseOptimizerMixin:
                     torch.full(like.shape, init if st.from_init else 0.0,
                                dtype=like.dtype, device=like.device),
                     persistent=True)
+            if rule in ADAM_SPARSE_OPTIMIZERS:
+                if not hasattr(self, "_adam_steps"):
+                    self._adam_steps = {}  # state prefix -> updates applied
+                    self.register_state_dict_pre_hook(_adam_steps_to_buffers)
+                    self.register_load_state_dict_pre_hook(
+                        _adam_steps_before_load)
+                    self.register_load_state_dict_post_hook(
+                        _adam_steps_from_buffers)
+                self._adam_steps[prefix] = 0
+                self.register_buffer(
+                    prefix + _ADAM_STEP,
+                    torch.zeros((), dtype=torch.int64, device=table.device),
+                    persistent=True)
+                names.append(prefix + _ADAM_STEP)
             acc = ("_adagrad_acc" if n_stateful == 0
                    else f"_adagrad_acc{n_stateful}")
             self.register_buffer(acc, None, persistent=False)
@@ -163,12 +228,25 @@ class SparseOptimizerMixin:
     def _sparse_side(self, rule: str, prefix: str, table: torch.Tensor,
                      grad: torch.Tensor, lr: float) -> "ops.SparseSide":
         """A table's side of a stateful update (``rule`` is not "sgd") with
-        this module's state buffers ``<prefix>...`` and scalars."""
+        this module's state buffers ``<prefix>...`` and scalars.  Every
+        applied update of a table builds exactly one side, so this is where
+        a lazy-Adam table's step count advances."""
+        adam = {}
+        if rule in ADAM_SPARSE_OPTIMIZERS:
+            self._adam_steps[prefix] += 1
+            adam = dict(beta1=self.sparse_betas[0],
+                        beta2=self.sparse_betas[1],
+                        step=self._adam_steps[prefix])
         return ops.SparseSide(
             rule, table,
             tuple(getattr(self, prefix + st.name)
                   for st in _RULE_STATES[rule]),
-            grad, lr, self.sparse_eps, self.sparse_l1, self.sparse_l2)
+            grad, lr, self.sparse_eps, self.sparse_l1, self.sparse_l2, **adam)
+
+    def adam_step_count(self, prefix: str = "") -> int:
+        """Updates applied so far to the lazy-Adam table whose state lives
+        under ``prefix`` (``""`` or ``"wide_"``)."""
+        return self._adam_steps[prefix]
 
     def _sparse_apply_one(self, rule: str, prefix: str,
                           table: torch.Tensor, ids: torch.Tensor,
@@ -255,14 +333,17 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
     sparse FTRL-proximal (``ftrl_accum`` / ``ftrl_linear``, regularised
     by ``sparse_l1`` / ``sparse_l2``), ``"rowwise_adagrad"`` (``dim > 1``)
     with row-wise sparse Adagrad, whose whole state is one fp32 value per
-    row (``state_sum_row``).
+    row (``state_sum_row``), ``"lazy_adam"`` with lazy Adam
+    (``adam_exp_avg`` / ``adam_exp_avg_sq`` / ``adam_step``, betas from
+    ``sparse_betas``).
     """
 
     def __init__(self, table_sizes: List[int], dim: int,
                  out_bf16: bool = False, init_std: Optional[float] = None,
                  sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
                  sparse_initial_accumulator: float = 0.0,
-                 sparse_l1: float = 0.0, sparse_l2: float = 0.0):
+                 sparse_l1: float = 0.0, sparse_l2: float = 0.0,
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.dim = dim
@@ -281,7 +362,8 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         self._init_sparse_optimizer(
             sparse_eps, sparse_initial_accumulator,
             {"": (self.weight, sparse_optimizer)},
-            sparse_l1=sparse_l1, sparse_l2=sparse_l2)
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2,
+            sparse_betas=sparse_betas)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -381,7 +463,8 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
     scatter-add sparse update (the wide part of wide-and-deep);
     ``sparse_optimizer="adagrad"`` switches the update to sparse
     Adagrad, ``"ftrl"`` to sparse FTRL-proximal (the canonical rule for
-    this table; ``sparse_l1 > 0`` leaves exact zeros).  ``wide_sparse_lr``
+    this table; ``sparse_l1 > 0`` leaves exact zeros), ``"lazy_adam"`` to
+    lazy Adam.  ``wide_sparse_lr``
     fixes this table's lr whatever ``apply_sparse_updates`` is given."""
 
     def __init__(self, table_sizes: List[int], out_bf16: bool = False,
@@ -389,7 +472,8 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
                  sparse_eps: float = 1e-10,
                  sparse_initial_accumulator: float = 0.0,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 wide_sparse_lr: Optional[float] = None):
+                 wide_sparse_lr: Optional[float] = None,
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.out_bf16 = out_bf16
@@ -406,7 +490,7 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
             sparse_eps, sparse_initial_accumulator,
             {"": (self.weight, sparse_optimizer)},
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
-            wide_sparse_lr=wide_sparse_lr)
+            wide_sparse_lr=wide_sparse_lr, sparse_betas=sparse_betas)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor) -> torch.Tensor:
@@ -570,8 +654,9 @@ class WideAndDeep(nn.Module):
                  sparse_initial_accumulator: float = 0.0,
                  wide_sparse_optimizer: Optional[str] = None,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 wide_sparse_lr: Optional[float] = None):
-        """``sparse_optimizer`` ("sgd", "adagrad", "ftrl" or
+                 wide_sparse_lr: Optional[float] = None,
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
+        """``sparse_optimizer`` ("sgd", "adagrad", "ftrl", "lazy_adam" or
         "rowwise_adagrad") picks the update rule of the embedding tables;
         it is NOT inferred from the dense optimizer, whose lr is what
         ``apply_sparse_updates(lr)`` receives.  ``wide_sparse_optimizer``
@@ -592,7 +677,15 @@ class WideAndDeep(nn.Module):
         ``wide_sparse_lr``: when set, the wide table runs at this fixed
         lr instead of the one passed to ``apply_sparse_updates``.
         ``sparse_initial_accumulator`` fills Adagrad's ``state_sum`` and
-        FTRL's ``ftrl_accum`` alike; TF's default for both is 0.1."""
+        FTRL's ``ftrl_accum`` alike; TF's default for both is 0.1.
+
+        ``"lazy_adam"`` (any table; the wide table follows the deep one by
+        default) is ``torch.optim.SparseAdam`` / TF ``LazyAdam``: only the
+        batch's rows move, with ``sparse_betas`` and one step count per
+        table that checkpoints carry (``adam_step``).  Its ``eps`` is
+        ``sparse_eps``, whose default 1e-10 is Adagrad's (Adam's usual is
+        1e-8), outside the square root; its two states start at 0 and
+        ignore ``sparse_initial_accumulator``."""
         super().__init__()
         table_sizes = table_sizes or DEFAULT_TABLE_SIZES
         if wide_sparse_optimizer is None:
@@ -600,7 +693,8 @@ class WideAndDeep(nn.Module):
         sparse_kw = dict(
             sparse_optimizer=sparse_optimizer, sparse_eps=sparse_eps,
             sparse_initial_accumulator=sparse_initial_accumulator,
-            sparse_l1=sparse_l1, sparse_l2=sparse_l2)
+            sparse_l1=sparse_l1, sparse_l2=sparse_l2,
+            sparse_betas=sparse_betas)
         self.sparse_optimizer = sparse_optimizer
         self.wide_sparse_optimizer = wide_sparse_optimizer
         self.compute_dtype = compute_dtype
@@ -758,7 +852,8 @@ class FlatInputWideAndDeep(nn.Module):
                  sparse_initial_accumulator: float = 0.0,
                  wide_sparse_optimizer: Optional[str] = None,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 wide_sparse_lr: Optional[float] = None):
+                 wide_sparse_lr: Optional[float] = None,
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
         """The sparse-optimizer arguments are :class:`WideAndDeep`'s."""
         super().__init__()
         self.dense_dim = dense_dim
@@ -770,6 +865,7 @@ class FlatInputWideAndDeep(nn.Module):
                                wide_sparse_optimizer=wide_sparse_optimizer,
                                sparse_l1=sparse_l1, sparse_l2=sparse_l2,
                                wide_sparse_lr=wide_sparse_lr,
+                               sparse_betas=sparse_betas,
                                table_sizes=table_sizes,
                                embedding_dim=embedding_dim, hidden=hidden,
                                compute_dtype=compute_dtype,

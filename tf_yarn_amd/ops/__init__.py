@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import functools
 import logging
+import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -348,7 +349,7 @@ def emb_bwd_dense(grad_table: torch.Tensor, ids: torch.Tensor,
                           alpha=scale)
 
 
-# ---- stateful sparse updates (Adagrad, FTRL, row-wise Adagrad) -------------
+# ---- stateful sparse updates (Adagrad, FTRL, lazy Adam, row-wise Adagrad) --
 
 class SparseWorkspace:
     """Device scratch of the accumulate-then-claim sparse kernels for one
@@ -464,13 +465,57 @@ def _rowwise_adagrad_rows_ref(table: torch.Tensor, state_row: torch.Tensor,
     table.index_copy_(0, uniq, w)
 
 
+def _check_lazy_adam_args(lr: float, eps: float, beta1: float, beta2: float,
+                          step: int) -> None:
+    if not lr > 0:
+        raise ValueError(f"lazy Adam needs lr > 0, got {lr!r}")
+    if not (0 <= beta1 < 1 and 0 <= beta2 < 1):
+        raise ValueError("lazy Adam needs 0 <= beta < 1 for both betas, got "
+                         f"beta1={beta1!r}, beta2={beta2!r}")
+    if not eps >= 0:
+        raise ValueError(f"lazy Adam needs eps >= 0, got {eps!r}")
+    if not (isinstance(step, int) and step >= 1):
+        raise ValueError(
+            "lazy Adam needs an int step >= 1 (the count of updates applied "
+            f"to the table, this one included), got {step!r}")
+
+
+def _lazy_adam_rows_ref(table: torch.Tensor, exp_avg: torch.Tensor,
+                        exp_avg_sq: torch.Tensor, flat_ids: torch.Tensor,
+                        rows: torch.Tensor, lr: float, eps: float,
+                        beta1: float, beta2: float, step: int,
+                        scale: float) -> None:
+    """Reference: coalesce duplicate ids, then one Adam step on the unique
+    rows ONLY (== torch.optim.SparseAdam on a coalesced sparse grad), in
+    fp32 and in the kernel's operation order.  ``step_size`` and the two
+    ``1 - beta`` are formed in Python floats (double) and rounded to fp32
+    once, where they meet the tensors."""
+    uniq, inv = torch.unique(flat_ids, return_inverse=True)
+    g = torch.zeros(uniq.numel(), rows.shape[1], dtype=torch.float32,
+                    device=rows.device)
+    g.index_add_(0, inv, rows.float())
+    g.mul_(scale)
+    step_size = (lr * math.sqrt(1.0 - beta2 ** step)
+                 / (1.0 - beta1 ** step))
+    m = exp_avg.index_select(0, uniq)
+    v = exp_avg_sq.index_select(0, uniq)
+    m = m + (1.0 - beta1) * (g - m)
+    v = v + (1.0 - beta2) * (g * g - v)
+    w = table.index_select(0, uniq) - (step_size * m) / (v.sqrt() + eps)
+    exp_avg.index_copy_(0, uniq, m)
+    exp_avg_sq.index_copy_(0, uniq, v)
+    table.index_copy_(0, uniq, w)
+
+
 class SparseSide(NamedTuple):
     """One table's side of a stateful sparse update: the rule (``"adagrad"``,
-    ``"ftrl"`` or ``"rowwise_adagrad"``), the table, the rule's state tensors
-    in the rule's order (``(state_sum,)``, ``(accum, linear)``,
-    ``(state_row,)``), the gradient (deep: ``[n, dim]``; wide: per example,
-    ``gw[i // g_div]``) and the rule's scalars; a rule ignores the scalars
-    it does not have."""
+    ``"ftrl"``, ``"lazy_adam"`` or ``"rowwise_adagrad"``), the table, the
+    rule's state tensors in the rule's order (``(state_sum,)``, ``(accum,
+    linear)``, ``(exp_avg, exp_avg_sq)``, ``(state_row,)``), the gradient
+    (deep: ``[n, dim]``; wide: per example, ``gw[i // g_div]``) and the
+    rule's scalars; a rule ignores the scalars it does not have.
+    ``beta1``, ``beta2`` and ``step`` are lazy Adam's: ``step`` is the count
+    of updates applied to the table, this one included (>= 1)."""
     rule: str
     table: torch.Tensor
     states: Tuple[torch.Tensor, ...]
@@ -479,6 +524,9 @@ class SparseSide(NamedTuple):
     eps: float = 1e-10
     l1: float = 0.0
     l2: float = 0.0
+    beta1: float = 0.9
+    beta2: float = 0.999
+    step: int = 0
 
 
 def _side_ref(side: SparseSide, flat: torch.Tensor, is_wide: bool,
@@ -499,6 +547,9 @@ def _side_ref(side: SparseSide, flat: torch.Tensor, is_wide: bool,
                        scale)
     elif side.rule == "adagrad":
         _adagrad_rows_ref(*tensors, flat, rows, side.lr, side.eps, scale)
+    elif side.rule == "lazy_adam":
+        _lazy_adam_rows_ref(*tensors, flat, rows, side.lr, side.eps,
+                            side.beta1, side.beta2, side.step, scale)
     else:
         _rowwise_adagrad_rows_ref(side.table, side.states[0], flat, rows,
                                   side.lr, side.eps, scale)
@@ -506,8 +557,10 @@ def _side_ref(side: SparseSide, flat: torch.Tensor, is_wide: bool,
 
 def _side_arg(side: SparseSide, acc: torch.Tensor) -> tuple:
     """A side as ``_C.emb_bwd_sparse`` takes it."""
-    rule, table, states, grad, lr, eps, l1, l2 = side
-    return (rule, table, states, acc, grad.contiguous(), lr, eps, l1, l2)
+    rule, table, states, grad, lr, eps, l1, l2, beta1, beta2, step = side
+    arg = (rule, table, states, acc, grad.contiguous(), lr, eps, l1, l2)
+    # lazy Adam's scalars ride behind the nine every rule has
+    return arg + (beta1, beta2, step) if rule == "lazy_adam" else arg
 
 
 @functools.lru_cache(maxsize=None)
@@ -542,6 +595,9 @@ def emb_bwd_sparse(ids: torch.Tensor, *, deep: Optional[SparseSide] = None,
     for side in sides:
         if side.rule == "ftrl":
             _check_ftrl_args(side.lr, side.l1, side.l2)
+        elif side.rule == "lazy_adam":
+            _check_lazy_adam_args(side.lr, side.eps, side.beta1, side.beta2,
+                                  side.step)
     flat = ids.reshape(-1)
     if not (ids.is_cuda or any(t.is_cuda for s in sides
                                for t in (s.table, s.grad, *s.states))):
@@ -703,6 +759,103 @@ def emb_bwd_ftrl_fused_wide(
     emb_bwd_sparse(
         ids, deep=SparseSide("ftrl", table, (accum, linear), grad, lr,
                              l1=l1, l2=l2),
+        wide=SparseSide("ftrl", wide_table, (wide_accum, wide_linear), gw,
+                        lr if wide_lr is None else wide_lr, l1=l1, l2=l2),
+        scale=scale, workspace=workspace)
+
+
+def emb_bwd_lazy_adam(table: torch.Tensor, exp_avg: torch.Tensor,
+                      exp_avg_sq: torch.Tensor, ids: torch.Tensor,
+                      grad: torch.Tensor, *, lr: float, step: int,
+                      beta1: float = 0.9, beta2: float = 0.999,
+                      eps: float = 1e-8, scale: float = 1.0,
+                      workspace: Optional[SparseWorkspace] = None) -> None:
+    """Lazy (sparse) Adam on the rows named by ``ids``:
+    ``torch.optim.SparseAdam`` on a coalesced gradient, TF's ``LazyAdam``.
+    For each unique id u, ``G = scale * sum(grad[i] for ids[i] == u)`` and
+    per element in fp32, with ``m = exp_avg[u]``, ``v = exp_avg_sq[u]``,
+    ``w = table[u]``::
+
+        m' = m + (1 - beta1) * (G - m)
+        v' = v + (1 - beta2) * (G*G - v)
+        w' = w - step_size * m' / (sqrt(v') + eps)
+        step_size = lr * sqrt(1 - beta2**step) / (1 - beta1**step)
+
+    ``step`` (required) is the number of updates applied to this table,
+    the current one included (first call: 1); it is one count per table,
+    not per row.  Rows not in ``ids`` are neither read nor written: their
+    ``m`` and ``v`` do not decay (that is "lazy"); a touched row whose
+    gradients sum to 0 still decays ``m`` and ``v`` and moves ``w``.
+    ``eps`` sits outside the square root and is not divided by the bias
+    correction, unlike :func:`fused_adam` (``torch.optim.Adam``'s form).
+    ``grad`` fp32 or bf16; table and both states fp32, any ``dim >= 1``.
+
+    GPU: the accumulate-then-claim kernels of :func:`emb_bwd_adagrad` with
+    the Adam rule (``csrc/sparse_adagrad.hip``); ``step_size`` and the two
+    ``1 - beta`` are formed on the host in double and rounded once."""
+    emb_bwd_sparse(ids, deep=SparseSide("lazy_adam", table,
+                                        (exp_avg, exp_avg_sq), grad, lr,
+                                        eps, beta1=beta1, beta2=beta2,
+                                        step=step),
+                   scale=scale, workspace=workspace)
+
+
+def emb_bwd_lazy_adam_wide(table: torch.Tensor, exp_avg: torch.Tensor,
+                           exp_avg_sq: torch.Tensor, ids: torch.Tensor,
+                           gw: torch.Tensor, *, lr: float, step: int,
+                           beta1: float = 0.9, beta2: float = 0.999,
+                           eps: float = 1e-8, scale: float = 1.0,
+                           workspace: Optional[SparseWorkspace] = None
+                           ) -> None:
+    """:func:`emb_bwd_lazy_adam` for the ``[rows, 1]`` wide table, with the
+    ``gw[i // g_div]`` gradient layout of :func:`emb_bwd_adagrad_wide`."""
+    emb_bwd_sparse(ids, wide=SparseSide("lazy_adam", table,
+                                        (exp_avg, exp_avg_sq), gw, lr, eps,
+                                        beta1=beta1, beta2=beta2, step=step),
+                   scale=scale, workspace=workspace)
+
+
+def emb_bwd_lazy_adam_fused_wide(
+        table: torch.Tensor, exp_avg: torch.Tensor,
+        exp_avg_sq: torch.Tensor, wide_table: torch.Tensor,
+        wide_exp_avg: torch.Tensor, wide_exp_avg_sq: torch.Tensor,
+        ids: torch.Tensor, grad: torch.Tensor, gw: torch.Tensor, *,
+        lr: float, step: int, wide_lr: Optional[float] = None,
+        wide_step: Optional[int] = None, beta1: float = 0.9,
+        beta2: float = 0.999, eps: float = 1e-8, scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """Lazy Adam on BOTH CTR tables from the shared flat ids (betas and
+    ``eps`` are shared; the wide table may run at its own ``wide_lr`` and
+    carries its own count ``wide_step``, default ``step``): one claim per
+    row for both.  ``workspace`` must have been built with ``wide_table``.
+    Fallback rule as in :func:`emb_bwd_adagrad_fused_wide`."""
+    emb_bwd_sparse(
+        ids, deep=SparseSide("lazy_adam", table, (exp_avg, exp_avg_sq), grad,
+                             lr, eps, beta1=beta1, beta2=beta2, step=step),
+        wide=SparseSide("lazy_adam", wide_table,
+                        (wide_exp_avg, wide_exp_avg_sq), gw,
+                        lr if wide_lr is None else wide_lr, eps, beta1=beta1,
+                        beta2=beta2,
+                        step=step if wide_step is None else wide_step),
+        scale=scale, workspace=workspace)
+
+
+def emb_bwd_lazy_adam_ftrl_fused_wide(
+        table: torch.Tensor, exp_avg: torch.Tensor,
+        exp_avg_sq: torch.Tensor, wide_table: torch.Tensor,
+        wide_accum: torch.Tensor, wide_linear: torch.Tensor,
+        ids: torch.Tensor, grad: torch.Tensor, gw: torch.Tensor, *,
+        lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999,
+        eps: float = 1e-8, wide_lr: Optional[float] = None, l1: float = 0.0,
+        l2: float = 0.0, scale: float = 1.0,
+        workspace: Optional[SparseWorkspace] = None) -> None:
+    """Lazy Adam (``lr``, betas, ``eps``, ``step``) on the deep table and
+    sparse FTRL (``wide_lr``, default ``lr``; ``l1``, ``l2``) on the wide
+    scalars from the shared flat ids, one claim per row for both.
+    Fallback rule as in :func:`emb_bwd_adagrad_ftrl_fused_wide`."""
+    emb_bwd_sparse(
+        ids, deep=SparseSide("lazy_adam", table, (exp_avg, exp_avg_sq), grad,
+                             lr, eps, beta1=beta1, beta2=beta2, step=step),
         wide=SparseSide("ftrl", wide_table, (wide_accum, wide_linear), gw,
                         lr if wide_lr is None else wide_lr, l1=l1, l2=l2),
         scale=scale, workspace=workspace)

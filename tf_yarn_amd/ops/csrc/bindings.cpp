@@ -2,6 +2,7 @@
 #include <torch/extension.h>
 #include <string>
 #include <tuple>
+#include <variant>
 #include <vector>
 
 // fused_optimizers.hip
@@ -64,11 +65,17 @@ void emb_scatter_sum(torch::Tensor table, torch::Tensor ids,
 
 // sparse_adagrad.hip
 // one table's side of a stateful sparse update: (rule name, table, state
-// tensors, accumulator, gradient or None, lr, eps, l1, l2)
-using SparseSide = std::tuple<std::string, torch::Tensor,
-                              std::vector<torch::Tensor>, torch::Tensor,
-                              c10::optional<torch::Tensor>, double, double,
-                              double, double>;
+// tensors, accumulator, gradient or None, lr, eps, l1, l2); a lazy_adam
+// side carries (beta1, beta2, step) after them
+using SparseSide9 = std::tuple<std::string, torch::Tensor,
+                               std::vector<torch::Tensor>, torch::Tensor,
+                               c10::optional<torch::Tensor>, double, double,
+                               double, double>;
+using SparseSide12 = std::tuple<std::string, torch::Tensor,
+                                std::vector<torch::Tensor>, torch::Tensor,
+                                c10::optional<torch::Tensor>, double, double,
+                                double, double, double, double, int64_t>;
+using SparseSide = std::variant<SparseSide9, SparseSide12>;
 void emb_bwd_sparse(c10::optional<SparseSide> deep,
                     c10::optional<SparseSide> wide, torch::Tensor stamp,
                     torch::Tensor ids, int64_t epoch, double scale);
@@ -172,7 +179,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
   m.def("emb_bwd_sparse", &emb_bwd_sparse,
-        "Stateful sparse update (adagrad, ftrl, rowwise_adagrad) of a deep "
+        "Stateful sparse update (adagrad, ftrl, rowwise_adagrad, lazy_adam) "
+        "of a deep "
         "side, a wide side or both from shared ids: atomic accumulate + "
         "once-per-row claim/apply; sides without gradients run the apply "
         "alone on their accumulators",

@@ -1,5 +1,5 @@
-// Stateful sparse optimizers for the embedding tables (Adagrad, FTRL,
-// row-wise Adagrad): accumulate, then claim.
+// Stateful sparse optimizers for the embedding tables (Adagrad, FTRL, lazy
+// Adam, row-wise Adagrad): accumulate, then claim.
 //
 // A stateful sparse optimizer must sum a batch's duplicate ids BEFORE it
 // touches the state, then update state and weight once per unique row
@@ -27,10 +27,13 @@
 //   kStates                how many table-shaped fp32 state tensors;
 //   one(g, s, w, a)        the per-element update: g the summed, scaled
 //                          gradient, s[kStates] the states, w the weight.
-// AdagradRule (1 state) and FtrlRule (2 states) are instantiated.  That
-// interface is per ELEMENT with table-shaped states: lazy Adam would be one
-// more such struct, its line in kRules and one line in kDispatch per pair
-// wanted; row-wise Adagrad is not.
+// AdagradRule (1 state), FtrlRule and AdamRule (2 states each) are
+// instantiated.  That interface is per ELEMENT with table-shaped states: lazy
+// Adam is one more such struct, its line in kRules and one line in kDispatch
+// per pair wanted; row-wise Adagrad is not.  What lazy Adam adds on the host
+// is its scalars: two betas and the table's step count t, which changes with
+// every update, so a lazy_adam side carries three more elements (SideArg12)
+// and the host folds them, in double, into step_size and the two (1 - beta).
 //
 // Entry points: emb_bwd_sparse, the one update entry (a deep side, a wide
 // side or both; with gradients pass 1 + pass 2, without them pass 2 alone),
@@ -62,9 +65,11 @@
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <cmath>
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <variant>
 #include <vector>
 #include "common.h"
 
@@ -109,6 +114,32 @@ struct FtrlRule {
     s[0] = n_new;
     s[1] = z;
     *w = fabsf(z) > a.l1 ? (copysignf(a.l1, z) - z) / q : 0.f;
+  }
+};
+
+// Lazy Adam (torch.optim.SparseAdam on a coalesced gradient, TF LazyAdam);
+// s[0] = m (exp_avg), s[1] = v (exp_avg_sq):
+//   m' = m + (1 - beta1) * (g - m);  v' = v + (1 - beta2) * (g*g - v);
+//   w' = w - step_size * m' / (sqrt(v') + eps),
+//   step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t), formed on the host.
+// eps sits outside the root and is not divided by the bias correction (the
+// dense fused_adam has torch.optim.Adam's form instead).  The multiply-adds
+// are written out (fmaf; the products that must round on their own as
+// __fmul_rn), so the quad kernel and the one-lane-per-row kernel give the
+// same bits for the same element whatever the compiler would contract.
+// One true division, one sqrtf, no clamp: sqrt(v') + eps == 0 needs
+// eps == 0 and v' == 0 (a fresh row whose gradient sums to 0), where the
+// quotient is 0/0 = NaN exactly as in torch; eps > 0 is the caller's guard.
+struct AdamRule {
+  struct Args { float step_size, eps, omb1, omb2; };
+  static constexpr int kStates = 2;  // exp_avg, exp_avg_sq
+  __device__ static __forceinline__ void one(float g, float (&s)[2],
+                                             float* w, Args a) {
+    const float m = fmaf(a.omb1, g - s[0], s[0]);
+    const float v = fmaf(a.omb2, __fmul_rn(g, g) - s[1], s[1]);
+    s[0] = m;
+    s[1] = v;
+    *w -= __fmul_rn(a.step_size, m) / (sqrtf(v) + a.eps);
   }
 };
 
@@ -319,7 +350,7 @@ __global__ void rowwise_adagrad_apply_row_kernel(
 
 using Tensors = std::vector<torch::Tensor>;
 
-enum RuleId { kAdagrad, kFtrl, kRowwiseAdagrad, kNoRule };
+enum RuleId { kAdagrad, kFtrl, kRowwiseAdagrad, kLazyAdam, kNoRule };
 
 // What the host knows about a rule: its name, how many state tensors it
 // takes, and whether a state holds one value per table row ([rows], row-wise
@@ -335,6 +366,7 @@ const RuleInfo kRules[] = {
     {"adagrad", kAdagrad, 1, false},
     {"ftrl", kFtrl, 2, false},
     {"rowwise_adagrad", kRowwiseAdagrad, 1, true},
+    {"lazy_adam", kLazyAdam, 2, false},
 };
 
 const RuleInfo& rule_named(const std::string& name) {
@@ -346,10 +378,17 @@ const RuleInfo& rule_named(const std::string& name) {
 
 // A side as the entry point takes it: (rule name, table, the rule's state
 // tensors in the rule's order, accumulator, gradient or None, lr, eps, l1,
-// l2).  A rule reads the scalars it has and ignores the others.
-using SideArg = std::tuple<std::string, torch::Tensor, Tensors,
-                           torch::Tensor, c10::optional<torch::Tensor>,
-                           double, double, double, double>;
+// l2).  A rule reads the scalars it has and ignores the others.  A lazy_adam
+// side, and only that, carries three more: beta1, beta2 and the step count t
+// of the update being applied (the first one is t = 1).
+using SideArg9 = std::tuple<std::string, torch::Tensor, Tensors,
+                            torch::Tensor, c10::optional<torch::Tensor>,
+                            double, double, double, double>;
+using SideArg12 = std::tuple<std::string, torch::Tensor, Tensors,
+                             torch::Tensor, c10::optional<torch::Tensor>,
+                             double, double, double, double, double, double,
+                             int64_t>;
+using SideArg = std::variant<SideArg9, SideArg12>;
 
 struct Side {
   const RuleInfo* rule;
@@ -358,11 +397,25 @@ struct Side {
   torch::Tensor acc;
   c10::optional<torch::Tensor> grad;
   double lr, eps, l1, l2;
+  double beta1 = 0.0, beta2 = 0.0;  // lazy_adam only
+  int64_t step = 0;
 };
 
 Side unpack(const SideArg& arg) {
-  const auto& [rule, table, states, acc, grad, lr, eps, l1, l2] = arg;
-  return {&rule_named(rule), table, states, acc, grad, lr, eps, l1, l2};
+  if (const auto* a9 = std::get_if<SideArg9>(&arg)) {
+    const auto& [rule, table, states, acc, grad, lr, eps, l1, l2] = *a9;
+    const RuleInfo& info = rule_named(rule);
+    TORCH_CHECK(info.id != kLazyAdam, "a lazy_adam side takes 12 elements: "
+                "beta1, beta2 and step after l2");
+    return {&info, table, states, acc, grad, lr, eps, l1, l2};
+  }
+  const auto& [rule, table, states, acc, grad, lr, eps, l1, l2, beta1, beta2,
+               step] = std::get<SideArg12>(arg);
+  const RuleInfo& info = rule_named(rule);
+  TORCH_CHECK(info.id == kLazyAdam, "only a lazy_adam side takes beta1, "
+              "beta2 and step; '", info.name, "' takes 9 elements");
+  return {&info, table, states, acc, grad, lr, eps, l1, l2, beta1, beta2,
+          step};
 }
 
 // ---- host: checks -----------------------------------------------------------
@@ -397,6 +450,16 @@ void check_ftrl_args(double lr, double l1, double l2) {
   TORCH_CHECK(l1 >= 0.0 && l2 >= 0.0, "FTRL needs l1 >= 0 and l2 >= 0");
 }
 
+void check_adam_args(double lr, double eps, double beta1, double beta2,
+                     int64_t step) {
+  TORCH_CHECK(lr > 0.0, "lazy Adam needs lr > 0");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "lazy Adam needs 0 <= beta < 1 for both betas");
+  TORCH_CHECK(eps >= 0.0, "lazy Adam needs eps >= 0");
+  TORCH_CHECK(step >= 1, "lazy Adam needs step >= 1 (the count of updates "
+              "applied to the table, this one included)");
+}
+
 // dim/4 as a shift when the quad kernel's lane-sharing rule holds, else -1
 int quad_shift(int64_t dim) {
   if (dim % 4 != 0) return -1;
@@ -413,6 +476,8 @@ int quad_shift(int64_t dim) {
 void check_side(const Side& s, int64_t deep_rows) {
   const bool companion = deep_rows >= 0;
   if (s.rule->id == kFtrl) check_ftrl_args(s.lr, s.l1, s.l2);
+  if (s.rule->id == kLazyAdam)
+    check_adam_args(s.lr, s.eps, s.beta1, s.beta2, s.step);
   if (companion) {
     TORCH_CHECK(s.table.is_cuda() && s.table.is_contiguous() &&
                 s.table.scalar_type() == torch::kFloat32 &&
@@ -484,12 +549,26 @@ FtrlRule::Args ftrl_args(double lr, double l1, double l2) {
   return {(float)lr, (float)l1, (float)l2};
 }
 
+// Formed in double and rounded once: 1.f - (float)beta would carry the
+// rounding error of beta into a number a hundred times smaller.
+AdamRule::Args adam_args(double lr, double eps, double beta1, double beta2,
+                         int64_t step) {
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
+  return {(float)(lr * std::sqrt(bc2) / bc1), (float)eps,
+          (float)(1.0 - beta1), (float)(1.0 - beta2)};
+}
+
 template <typename Rule> typename Rule::Args rule_args(const Side& s);
 template <> AdagradRule::Args rule_args<AdagradRule>(const Side& s) {
   return adagrad_args(s.lr, s.eps);
 }
 template <> FtrlRule::Args rule_args<FtrlRule>(const Side& s) {
   return ftrl_args(s.lr, s.l1, s.l2);
+}
+
+template <> AdamRule::Args rule_args<AdamRule>(const Side& s) {
+  return adam_args(s.lr, s.eps, s.beta1, s.beta2, s.step);
 }
 
 // The wide companion's kernel arguments; all null under NoRule.
@@ -598,6 +677,9 @@ const Dispatch kDispatch[] = {
     {kFtrl, kFtrl, launch_elementwise<FtrlRule, FtrlRule>},
     {kRowwiseAdagrad, kAdagrad, launch_rowwise<AdagradRule>},
     {kRowwiseAdagrad, kFtrl, launch_rowwise<FtrlRule>},
+    {kLazyAdam, kNoRule, launch_elementwise<AdamRule, NoRule>},
+    {kLazyAdam, kLazyAdam, launch_elementwise<AdamRule, AdamRule>},
+    {kLazyAdam, kFtrl, launch_elementwise<AdamRule, FtrlRule>},
 };
 
 const Dispatch* find_dispatch(RuleId deep, RuleId wide) {
@@ -622,6 +704,7 @@ bool sparse_pair_fused_ok(const std::string& deep_rule,
 // rule, once per row:
 //   adagrad          state += G^2, table -= lr * G / (sqrt(state) + eps)
 //   ftrl             FtrlRule::one per element on (accum, linear, table)
+//   lazy_adam        AdamRule::one per element on (exp_avg, exp_avg_sq, table)
 //   rowwise_adagrad  state_row[u] += sum_c G[u, c]^2 / dim,
 //                    table[u, :] -= lr * G[u, :] / (sqrt(state_row[u]) + eps)
 // The wide gradient is per example, in the gw[i / g_div] layout of
