@@ -305,6 +305,72 @@ class SparseOptimizerMixin:
         return ws
 
 
+def _check_combiner(combiner: str) -> str:
+    if combiner not in ops.COMBINERS:
+        raise ValueError(
+            f"combiner must be one of {ops.COMBINERS}, got {combiner!r}")
+    return combiner
+
+
+class BagUpdate(NamedTuple):
+    """A sink entry that came from bags (``forward(..., bag_offsets=...)``):
+    ``(flat_ids [nnz], grad_rows [nnz, dim])`` like every other entry, but
+    ``nnz`` differs from rank to rank, so its data-parallel gather is the
+    padded one of :func:`_ragged_all_gather`."""
+    flat_ids: torch.Tensor
+    grad_rows: torch.Tensor
+
+
+def _ragged_all_gather(flat_ids: torch.Tensor, rows: torch.Tensor,
+                       world: int, process_group):
+    """Gather update lists whose length differs by rank.
+    ``all_gather_into_tensor`` needs equal counts, so the per-rank counts
+    are gathered first (one small collective and one ``.tolist()``, a host
+    sync, per table and step), then ids and rows are zero-padded to the
+    maximum and gathered asynchronously.  Returns ``(all_ids, all_rows,
+    works, counts)``; :func:`_valid_prefixes` drops the padding again, so
+    it never reaches an update op."""
+    n = flat_ids.numel()
+    count = torch.tensor([n], dtype=torch.int64, device=flat_ids.device)
+    all_counts = torch.empty(world, dtype=torch.int64,
+                             device=flat_ids.device)
+    dist.all_gather_into_tensor(all_counts, count, group=process_group)
+    counts = all_counts.tolist()
+    m = max(counts)
+    all_ids = torch.empty(m * world, dtype=flat_ids.dtype,
+                          device=flat_ids.device)
+    all_rows = torch.empty((m * world,) + tuple(rows.shape[1:]),
+                           dtype=rows.dtype, device=rows.device)
+    if m == 0:
+        return all_ids, all_rows, [], counts
+    ids_p = flat_ids.new_zeros(m)
+    ids_p[:n] = flat_ids
+    rows_p = rows.new_zeros((m,) + tuple(rows.shape[1:]))
+    rows_p[:n] = rows
+    works = [
+        dist.all_gather_into_tensor(all_ids, ids_p, group=process_group,
+                                    async_op=True),
+        dist.all_gather_into_tensor(all_rows, rows_p, group=process_group,
+                                    async_op=True),
+    ]
+    return all_ids, all_rows, works, counts
+
+
+def _valid_prefixes(all_ids: torch.Tensor, all_rows: torch.Tensor,
+                    counts: Optional[List[int]]):
+    """Each rank's valid prefix of a padded gather, concatenated (the
+    gather itself when ``counts`` is None: an equal-count entry)."""
+    if counts is None:
+        return all_ids, all_rows
+    m = all_ids.numel() // len(counts)
+    if all(c == m for c in counts):
+        return all_ids, all_rows
+    return (torch.cat([all_ids[r * m:r * m + c]
+                       for r, c in enumerate(counts)]),
+            torch.cat([all_rows[r * m:r * m + c]
+                       for r, c in enumerate(counts)]))
+
+
 class _FusedLookup(torch.autograd.Function):
     """Gather via the HIP kernel; backward stashes sparse (ids, grad)."""
 
@@ -325,7 +391,12 @@ class _FusedLookup(torch.autograd.Function):
 class SparseEmbedding(SparseOptimizerMixin, nn.Module):
     """Fused multi-table embedding with sparse-allgather DP sync.
 
-    ``forward(ids [B, F])`` -> ``[B, F*dim]``.
+    ``forward(ids [B, F])`` -> ``[B, F*dim]``.  Multi-hot features:
+    ``forward(ids [nnz], bag_offsets [B*F + 1], weights=None)`` pools bag
+    ``(b, f)`` with ``combiner`` ("sum", "mean" or "sqrtn";
+    :func:`tf_yarn_amd.ops.emb_bag_fwd` has the definition) into the same
+    ``[B, F*dim]``; its backward puts ``(flat_ids [nnz], grad_rows [nnz,
+    dim])`` into the sink, which every sparse rule consumes unchanged.
     After ``loss.backward()`` call :meth:`apply_sparse_updates` (the
     training loop or the framework optimizer wrapper does this).
     ``sparse_optimizer="adagrad"`` replaces the scatter+SGD update with
@@ -343,10 +414,12 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
                  sparse_optimizer: str = "sgd", sparse_eps: float = 1e-10,
                  sparse_initial_accumulator: float = 0.0,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999),
+                 combiner: str = "sum"):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.dim = dim
+        self.combiner = _check_combiner(combiner)
         self.out_bf16 = out_bf16
         total = sum(table_sizes)
         offsets = torch.tensor(
@@ -366,7 +439,14 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
             sparse_betas=sparse_betas)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
-    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor,
+                bag_offsets: Optional[torch.Tensor] = None,
+                weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if bag_offsets is not None:
+            return ops.EmbeddingBagFn.apply(
+                self.weight, ids, bag_offsets, len(self.table_sizes),
+                self.offsets, weights, self.combiner, self.out_bf16,
+                self._sink, None, 0, BagUpdate._make)
         b, f = ids.shape
         assert f == len(self.table_sizes), "feature count mismatch"
         flat = (ids + self.offsets.unsqueeze(0)).reshape(-1)
@@ -384,10 +464,16 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         world = (dist.get_world_size(process_group)
                  if dist.is_available() and dist.is_initialized() else 1)
         self._pending_world = world
-        self._gathered: List[Tuple[torch.Tensor, torch.Tensor, list]] = []
-        for flat_ids, grad in self._sink:
+        self._gathered: List[tuple] = []
+        for entry in self._sink:
+            flat_ids, grad = entry
             grad2d = grad.reshape(flat_ids.numel(), self.dim)
-            if world > 1:
+            if world > 1 and isinstance(entry, BagUpdate):
+                # nnz differs by rank: counts first (a host sync), then
+                # the padded gather
+                self._gathered.append(_ragged_all_gather(
+                    flat_ids, grad2d, world, process_group))
+            elif world > 1:
                 n = flat_ids.numel()
                 all_ids = torch.empty(n * world, dtype=flat_ids.dtype,
                                       device=flat_ids.device)
@@ -402,9 +488,14 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
                                                 group=process_group,
                                                 async_op=True),
                 ]
-                self._gathered.append((all_ids, all_grads, works))
+                self._gathered.append((all_ids, all_grads, works, None))
             else:
-                self._gathered.append((flat_ids, grad2d, []))
+                # a bag entry carries its count, the mark that lets an
+                # all-empty one be skipped
+                self._gathered.append((
+                    flat_ids, grad2d, [],
+                    [flat_ids.numel()] if isinstance(entry, BagUpdate)
+                    else None))
         self._sink.clear()
 
     @torch.no_grad()
@@ -412,9 +503,13 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
         """Wait for the allgathers and apply the fused scatter+SGD (or
         sparse Adagrad) update scaled by 1/world_size."""
         world = getattr(self, "_pending_world", 1)
-        for all_ids, all_grads, works in getattr(self, "_gathered", []):
+        for all_ids, all_grads, works, counts in getattr(self, "_gathered",
+                                                         []):
             for w in works:
                 w.wait()
+            all_ids, all_grads = _valid_prefixes(all_ids, all_grads, counts)
+            if counts is not None and all_ids.numel() == 0:
+                continue  # every bag on every rank was empty
             if self.sparse_optimizer != "sgd":
                 self._sparse_apply_one(
                     self.sparse_optimizer, "", self.weight.data, all_ids,
@@ -465,7 +560,13 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
     Adagrad, ``"ftrl"`` to sparse FTRL-proximal (the canonical rule for
     this table; ``sparse_l1 > 0`` leaves exact zeros), ``"lazy_adam"`` to
     lazy Adam.  ``wide_sparse_lr``
-    fixes this table's lr whatever ``apply_sparse_updates`` is given."""
+    fixes this table's lr whatever ``apply_sparse_updates`` is given.
+
+    Multi-hot features: ``forward(ids [nnz], bag_offsets [B*F + 1],
+    weights=None)`` pools every bag at dim 1 with ``combiner``
+    (:func:`tf_yarn_amd.ops.emb_bag_fwd`, fp32) and sums the pooled
+    ``[B, F]`` over ``f = 0 .. F-1`` into the wide logit; the sink then
+    holds ``(flat_ids [nnz], grad [nnz])``, one id per gradient."""
 
     def __init__(self, table_sizes: List[int], out_bf16: bool = False,
                  init_std: float = 0.01, sparse_optimizer: str = "sgd",
@@ -473,10 +574,12 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
                  sparse_initial_accumulator: float = 0.0,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
                  wide_sparse_lr: Optional[float] = None,
-                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999),
+                 combiner: str = "sum"):
         super().__init__()
         self.table_sizes = list(table_sizes)
         self.out_bf16 = out_bf16
+        self.combiner = _check_combiner(combiner)
         total = sum(table_sizes)
         offsets = torch.tensor(
             [0] + list(torch.cumsum(torch.tensor(table_sizes), 0)[:-1]),
@@ -493,11 +596,27 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
             wide_sparse_lr=wide_sparse_lr, sparse_betas=sparse_betas)
         self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
-    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor,
+                bag_offsets: Optional[torch.Tensor] = None,
+                weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if bag_offsets is not None:
+            # pooled in fp32 and rounded once after the sum over features,
+            # as the one-hot gather-sum rounds
+            pooled = ops.EmbeddingBagFn.apply(
+                self.weight, ids, bag_offsets, len(self.table_sizes),
+                self.offsets, weights, self.combiner, False, self._sink,
+                None, 0, self._bag_update)
+            out = pooled.sum(dim=1)
+            return out.to(torch.bfloat16) if self.out_bf16 else out
         b = ids.shape[0]
         flat = (ids + self.offsets.unsqueeze(0)).reshape(-1)
         return _GatherSum.apply(self.weight, flat, b, self.out_bf16,
                                 self._sink)
+
+    @staticmethod
+    def _bag_update(entry) -> BagUpdate:
+        flat_ids, rows = entry
+        return BagUpdate(flat_ids, rows.reshape(-1))  # [nnz, 1] -> [nnz]
 
     def pending_grads(self):
         return self._sink
@@ -508,8 +627,12 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
                  if dist.is_available() and dist.is_initialized() else 1)
         self._pending_world = world
         self._gathered = []
-        for flat_ids, grad in self._sink:
-            if world > 1:
+        for entry in self._sink:
+            flat_ids, grad = entry
+            if world > 1 and isinstance(entry, BagUpdate):
+                self._gathered.append(_ragged_all_gather(
+                    flat_ids, grad.reshape(-1), world, process_group))
+            elif world > 1:
                 n = flat_ids.numel()
                 b = grad.numel()
                 all_ids = torch.empty(n * world, dtype=flat_ids.dtype,
@@ -525,9 +648,12 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
                                                 group=process_group,
                                                 async_op=True),
                 ]
-                self._gathered.append((all_ids, all_grads, works))
+                self._gathered.append((all_ids, all_grads, works, None))
             else:
-                self._gathered.append((flat_ids, grad.reshape(-1), []))
+                self._gathered.append((
+                    flat_ids, grad.reshape(-1), [],
+                    [flat_ids.numel()] if isinstance(entry, BagUpdate)
+                    else None))
         self._sink.clear()
 
     @torch.no_grad()
@@ -535,9 +661,13 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
         world = getattr(self, "_pending_world", 1)
         if self.wide_sparse_lr is not None:
             lr = self.wide_sparse_lr
-        for all_ids, all_grads, works in getattr(self, "_gathered", []):
+        for all_ids, all_grads, works, counts in getattr(self, "_gathered",
+                                                         []):
             for w in works:
                 w.wait()
+            all_ids, all_grads = _valid_prefixes(all_ids, all_grads, counts)
+            if counts is not None and all_ids.numel() == 0:
+                continue
             if self.sparse_optimizer != "sgd":
                 self._sparse_apply_one(
                     self.sparse_optimizer, "", self.weight.data, all_ids,
@@ -655,7 +785,8 @@ class WideAndDeep(nn.Module):
                  wide_sparse_optimizer: Optional[str] = None,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
                  wide_sparse_lr: Optional[float] = None,
-                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999),
+                 combiner: str = "sum"):
         """``sparse_optimizer`` ("sgd", "adagrad", "ftrl", "lazy_adam" or
         "rowwise_adagrad") picks the update rule of the embedding tables;
         it is NOT inferred from the dense optimizer, whose lr is what
@@ -685,9 +816,15 @@ class WideAndDeep(nn.Module):
         table that checkpoints carry (``adam_step``).  Its ``eps`` is
         ``sparse_eps``, whose default 1e-10 is Adagrad's (Adam's usual is
         1e-8), outside the square root; its two states start at 0 and
-        ignore ``sparse_initial_accumulator``."""
+        ignore ``sparse_initial_accumulator``.
+
+        ``combiner`` ("sum", "mean" or "sqrtn") pools multi-hot features:
+        ``forward(dense, ids [nnz], labels, bag_offsets=[B*F + 1],
+        sparse_weights=None)`` (replicated tables only; the one-hot call
+        ``forward(dense, ids [B, F])`` is unchanged and ignores it)."""
         super().__init__()
         table_sizes = table_sizes or DEFAULT_TABLE_SIZES
+        self.combiner = _check_combiner(combiner)
         if wide_sparse_optimizer is None:
             wide_sparse_optimizer = _default_wide_rule(sparse_optimizer)
         sparse_kw = dict(
@@ -714,10 +851,11 @@ class WideAndDeep(nn.Module):
         else:
             self.embeddings = None
             self.deep_embedding = SparseEmbedding(
-                table_sizes, embedding_dim, out_bf16=bf16, **sparse_kw)
+                table_sizes, embedding_dim, out_bf16=bf16,
+                combiner=combiner, **sparse_kw)
             # Wide: one scalar weight per categorical id
             wide_kw = dict(sparse_kw, sparse_optimizer=wide_sparse_optimizer,
-                           wide_sparse_lr=wide_sparse_lr)
+                           wide_sparse_lr=wide_sparse_lr, combiner=combiner)
             self.wide_embedding = WideScalarEmbedding(table_sizes,
                                                       out_bf16=bf16,
                                                       **wide_kw)
@@ -774,11 +912,43 @@ class WideAndDeep(nn.Module):
                                          head.weight, head.bias)
 
     def forward(self, dense: torch.Tensor, sparse_ids: torch.Tensor,
-                labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+                labels: Optional[torch.Tensor] = None,
+                bag_offsets: Optional[torch.Tensor] = None,
+                sparse_weights: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
         """Returns logits [B], or — when ``labels`` is given — the mean
         BCEWithLogits loss with the 3-part logit sum fused into the loss
-        kernel (ops.bce_head_loss)."""
+        kernel (ops.bce_head_loss).
+
+        With ``bag_offsets`` (``[B*F + 1]``) the features are multi-hot:
+        ``sparse_ids`` is the flat ``[nnz]`` id array, bag ``b*F + f``
+        holds the ids of feature ``f`` of example ``b`` (optionally
+        weighted by ``sparse_weights [nnz]``) and is pooled by the model's
+        ``combiner``.  The MLP input is built in one buffer: the dense
+        columns, zeros up to ``_DeepInput.DENSE_PAD``, and the pooled
+        lookup written straight into the slice behind them."""
         dense = dense.to(self.compute_dtype)
+        if bag_offsets is not None:
+            if self.sharded:
+                raise NotImplementedError(
+                    "multi-hot input (bag_offsets) with sharded=True: the "
+                    "feature-sharded all-to-all of ragged bags is not "
+                    "built; use the replicated tables (sharded=False)")
+            emb = self.deep_embedding
+            deep_in = ops.EmbeddingBagFn.apply(
+                emb.weight, sparse_ids, bag_offsets, len(emb.table_sizes),
+                emb.offsets, sparse_weights, self.combiner,
+                self.compute_dtype == torch.bfloat16, emb._sink, dense,
+                _DeepInput.DENSE_PAD, BagUpdate._make)
+            deep_out = self._deep_tower(deep_in)
+            wide_emb = self.wide_embedding(
+                sparse_ids, bag_offsets, sparse_weights).to(deep_out.dtype)
+            wd = self.wide_dense(dense)
+            if labels is not None:
+                return ops.bce_head_loss(deep_out, wide_emb, wd, labels)
+            return deep_out + wide_emb + wd
+        if sparse_weights is not None:
+            raise ValueError("sparse_weights needs bag_offsets")
         if self.sharded:
             b = dense.shape[0]
             emb = self.embeddings

@@ -1073,6 +1073,282 @@ def emb_scatter_sum(table: torch.Tensor, ids: torch.Tensor,
                                  alpha=alpha)
 
 
+# ---- multi-hot embedding bags ----------------------------------------------
+
+COMBINERS = ("sum", "mean", "sqrtn")
+
+
+def _check_bags(ids: torch.Tensor, bag_offsets: torch.Tensor,
+                n_features: int, weights: Optional[torch.Tensor],
+                nnz: int) -> int:
+    """Shape checks shared by the CPU and HIP paths (nothing here waits
+    for a device); returns the number of examples ``B``."""
+    if n_features < 1:
+        raise ValueError(f"n_features must be >= 1, got {n_features!r}")
+    if bag_offsets.dtype != torch.int64 or bag_offsets.dim() != 1:
+        raise ValueError("bag_offsets must be a 1-D int64 tensor")
+    n_bags = bag_offsets.numel() - 1
+    if n_bags < 0 or n_bags % n_features:
+        raise ValueError(
+            f"bag_offsets must have B * n_features + 1 entries "
+            f"(n_features={n_features}), got {bag_offsets.numel()}")
+    if ids is not None and (ids.dtype != torch.int64 or ids.dim() != 1):
+        raise ValueError("ids must be the flat 1-D int64 [nnz] array")
+    if weights is not None:
+        if weights.dtype != torch.float32:
+            raise ValueError("weights must be fp32")
+        if weights.numel() != nnz:
+            raise ValueError(f"weights must have one entry per id: {nnz}, "
+                             f"got {weights.numel()}")
+    return n_bags // n_features
+
+
+def _debug_check_bags(bag_offsets: torch.Tensor, nnz: int) -> None:
+    """MIYARN_DEBUG_BOUNDS=1 on the CPU path (the HIP path checks the same
+    in C++): ``bag_offsets`` starts at 0, ends at ``nnz`` and never
+    decreases."""
+    if bag_offsets[0].item() != 0 or bag_offsets[-1].item() != nnz:
+        raise RuntimeError(
+            f"bag_offsets must start at 0 and end at nnz = {nnz}, got "
+            f"[{bag_offsets[0].item()} .. {bag_offsets[-1].item()}] "
+            "(MIYARN_DEBUG_BOUNDS check)")
+    if bag_offsets.numel() > 1 and (bag_offsets[1:]
+                                    - bag_offsets[:-1]).min().item() < 0:
+        raise RuntimeError("bag_offsets must be non-decreasing "
+                           "(MIYARN_DEBUG_BOUNDS check)")
+
+
+def _bounds_debug() -> bool:
+    return os.environ.get("MIYARN_DEBUG_BOUNDS", "") not in ("", "0")
+
+
+def _bag_lengths(bag_offsets: torch.Tensor):
+    return bag_offsets[:-1], bag_offsets[1:] - bag_offsets[:-1]
+
+
+def _emb_bag_fwd_ref(table, ids, bag_offsets, n_features, offsets, weights,
+                     combiner, out, col_offset):
+    """The definition on the CPU, fp32, in the kernel's operation order:
+    step j adds entry j of every bag that has one, so each bag's sum runs
+    in ascending entry order.  ``fmaf`` is a float64 multiply-add rounded
+    to fp32 (the product is exact in float64)."""
+    n_bags = bag_offsets.numel() - 1
+    dim = table.shape[1]
+    lo, lens = _bag_lengths(bag_offsets)
+    if offsets is not None:
+        feat = torch.arange(n_bags, device=ids.device) % n_features
+        flat = ids + torch.repeat_interleave(offsets[feat], lens)
+    else:
+        flat = ids
+    if _bounds_debug() and flat.numel():
+        mn, mx = flat.min().item(), flat.max().item()
+        if mn < 0 or mx >= table.shape[0]:
+            raise RuntimeError(
+                f"embedding ids out of range: [{mn}, {mx}] vs table rows "
+                f"{table.shape[0]} (MIYARN_DEBUG_BOUNDS check)")
+    acc = torch.zeros(n_bags, dim, dtype=torch.float32, device=table.device)
+    den = (torch.zeros(n_bags, dtype=torch.float32, device=table.device)
+           if weights is not None else lens.float())
+    active = torch.nonzero(lens > 0).reshape(-1)
+    j = 0
+    while active.numel():
+        pos = lo[active] + j
+        rows = table.index_select(0, flat[pos])
+        if weights is None:
+            acc[active] = acc[active] + rows
+        else:
+            w = weights[pos]
+            acc[active] = (w.double().unsqueeze(1) * rows.double()
+                           + acc[active].double()).float()
+            if combiner == "mean":
+                den[active] = den[active] + w
+            elif combiner == "sqrtn":
+                den[active] = den[active] + w * w
+        j += 1
+        active = active[lens[active] > j]
+    if combiner == "sum":
+        scale = (lens > 0).float()
+    else:
+        ok = (lens > 0) & (den != 0)
+        d = torch.where(ok, den, torch.ones_like(den))
+        if combiner == "sqrtn":  # through float64, rounded once
+            inv = (1.0 / d.double().sqrt()).float()
+        else:  # tensor / tensor: a correctly rounded fp32 division
+            inv = torch.ones_like(d) / d
+        scale = torch.where(ok, inv, torch.zeros_like(inv))
+        acc = acc * scale.unsqueeze(1)
+    out[:, col_offset:col_offset + n_features * dim] = \
+        acc.reshape(-1, n_features * dim).to(out.dtype)
+    return scale, flat
+
+
+def emb_bag_fwd(table: torch.Tensor, ids: torch.Tensor,
+                bag_offsets: torch.Tensor, n_features: int, *,
+                offsets: Optional[torch.Tensor] = None,
+                weights: Optional[torch.Tensor] = None,
+                combiner: str = "sum", out: Optional[torch.Tensor] = None,
+                col_offset: int = 0, out_bf16: bool = False):
+    """Pooled multi-hot lookup from CSR bags; returns ``(out, bag_scale,
+    flat_ids)``.
+
+    ``table [rows, dim]`` fp32; ``ids [nnz]`` int64, the raw per-feature
+    ids; ``bag_offsets [B * n_features + 1]`` int64, non-decreasing from 0
+    to ``nnz``.  Bag ``k = b * F + f`` holds entries ``bag_offsets[k] ..
+    bag_offsets[k+1] - 1`` and entry ``i`` names row ``ids[i] +
+    offsets[k % F]`` (``offsets [F]`` int64, optional).  ``weights [nnz]``
+    fp32 are inputs: no gradient flows to them.  Per bag and column, in
+    fp32::
+
+        acc = 0;  for i ascending:  acc = acc + row_i[c]            (no weights)
+                                    acc = fmaf(w_i, row_i[c], acc)  (weights)
+        out[b, col_offset + f*dim + c] = acc * bag_scale[k]
+
+    rounded once if ``out`` is bf16.  ``bag_scale`` (fp32, returned for
+    the backward) is 1 for ``"sum"``; ``1/len`` or ``1/sum w`` for
+    ``"mean"``; ``1/sqrt(len)`` or ``1/sqrt(sum w^2)`` for ``"sqrtn"``,
+    the sums in fp32 in entry order (``w * w`` rounded before it is
+    added; ``1/sqrt`` of the fp32 sum is taken in float64 and rounded
+    once, which keeps the scale within 1 ulp).  An empty bag, or a zero denominator,
+    has ``bag_scale`` 0 and an all-zero output: the convention of TF's
+    ``safe_embedding_lookup_sparse`` for empty bags, extended to a zero
+    weight sum, where TF would divide by zero.  The sum order is ascending
+    position in the bag and nothing else, so two calls agree to the bit and
+    a bag gives the same bits wherever it sits in the batch.
+
+    ``out`` (contiguous 2-D fp32/bf16) receives the ``[B, F * dim]`` block
+    at ``col_offset`` and keeps its other columns; ``out=None`` allocates
+    ``[B, F * dim]`` (bf16 with ``out_bf16``).  ``flat_ids`` is ``ids``
+    itself without ``offsets``.  ``nnz == 0`` is legal.  A long bag is
+    walked serially by one lane group (not tuned).  MIYARN_DEBUG_BOUNDS=1
+    also validates ``bag_offsets`` and the id range (waits for the
+    device)."""
+    if combiner not in COMBINERS:
+        raise ValueError(
+            f"combiner must be one of {COMBINERS}, got {combiner!r}")
+    batch = _check_bags(ids, bag_offsets, n_features, weights, ids.numel())
+    if offsets is not None and offsets.numel() != n_features:
+        raise ValueError("offsets must be int64 [n_features]")
+    dim = table.shape[1]
+    if out is None:
+        out = torch.empty(
+            batch, n_features * dim, device=table.device,
+            dtype=torch.bfloat16 if out_bf16 else torch.float32)
+        col_offset = 0
+    if (out.dim() != 2 or out.shape[0] != batch or col_offset < 0
+            or col_offset + n_features * dim > out.shape[1]):
+        raise ValueError(
+            f"the [{batch}, {n_features * dim}] block at column "
+            f"{col_offset} does not fit out {tuple(out.shape)}")
+    if _on_gpu(table, ids, out):
+        _require_ext()
+        bag_scale, flat = _C.emb_bag_fwd(table, ids, bag_offsets,
+                                         n_features, offsets, weights,
+                                         combiner, out, col_offset)
+        return out, bag_scale, flat
+    if _bounds_debug():
+        _debug_check_bags(bag_offsets, ids.numel())
+    bag_scale, flat = _emb_bag_fwd_ref(table, ids, bag_offsets, n_features,
+                                       offsets, weights, combiner, out,
+                                       col_offset)
+    return out, bag_scale, flat
+
+
+def emb_bag_bwd_rows(grad_out: torch.Tensor, bag_offsets: torch.Tensor,
+                     bag_scale: torch.Tensor, dim: int, n_features: int, *,
+                     weights: Optional[torch.Tensor] = None,
+                     col_offset: int = 0,
+                     nnz: Optional[int] = None) -> torch.Tensor:
+    """The backward of :func:`emb_bag_fwd` as update rows: for entry ``i``
+    of bag ``k = (b, f)``::
+
+        s_i = bag_scale[k]  (* w_i with weights: one fp32 multiply)
+        grad_rows[i, c] = grad_out[b, col_offset + f*dim + c] * s_i
+
+    rounded to ``grad_out``'s dtype (fp32 or bf16); ``"sum"`` without
+    weights is a copy, bit for bit.  ``grad_out`` is the whole ``[B,
+    cols]`` gradient, read in place at ``col_offset`` (rows may lie a
+    stride apart).  With ``flat_ids`` of the forward, ``grad_rows [nnz,
+    dim]`` is the update list every sparse update op takes; an id that
+    appears twice in a bag appears twice in it, and the update ops sum
+    it.  ``nnz`` (``ids.numel()`` of the forward) sizes the result; without
+    it and without ``weights`` the GPU path reads ``bag_offsets[-1]`` back
+    from the device, the only wait in these two ops."""
+    if nnz is None and weights is not None:
+        nnz = int(weights.numel())
+    batch = _check_bags(None, bag_offsets, n_features, weights, nnz)
+    if bag_scale.numel() != batch * n_features:
+        raise ValueError("bag_scale must have one entry per bag")
+    if (grad_out.dim() != 2 or grad_out.shape[0] != batch or col_offset < 0
+            or col_offset + n_features * dim > grad_out.shape[1]):
+        raise ValueError(
+            f"the [{batch}, {n_features * dim}] block at column "
+            f"{col_offset} does not fit grad_out {tuple(grad_out.shape)}")
+    if _on_gpu(grad_out, bag_offsets, bag_scale):
+        _require_ext()
+        if nnz is None:
+            nnz = int(bag_offsets[-1].item())
+        if grad_out.stride(1) != 1 or grad_out.stride(0) < grad_out.shape[1]:
+            grad_out = grad_out.contiguous()
+        return _C.emb_bag_bwd_rows(grad_out, bag_offsets, bag_scale, dim,
+                                   n_features, nnz, weights, col_offset)
+    _, lens = _bag_lengths(bag_offsets)
+    n_bags = batch * n_features
+    if _bounds_debug():
+        _debug_check_bags(bag_offsets, int(lens.sum().item()))
+    bag = torch.repeat_interleave(torch.arange(n_bags), lens)
+    s = bag_scale[bag]
+    if weights is not None:
+        s = s * weights
+    g = grad_out[:, col_offset:col_offset + n_features * dim] \
+        .reshape(n_bags, dim)[bag]
+    return (g.float() * s.unsqueeze(1)).to(grad_out.dtype)
+
+
+class EmbeddingBagFn(torch.autograd.Function):
+    """Pooled multi-hot lookup (:func:`emb_bag_fwd`) whose backward appends
+    ``(flat_ids [nnz], grad_rows [nnz, dim])`` to ``sink``: the update list
+    the sparse update ops consume.  With ``dense`` the result is the MLP
+    input ``[B, col_offset + F * dim]`` in one buffer: dense columns first,
+    zeros up to ``col_offset``, the pooled block in the slice.  ``wrap``
+    makes the sink entry from the ``(flat_ids, grad_rows)`` pair (``tuple``,
+    or a module's marker type).  All twelve arguments are positional."""
+
+    @staticmethod
+    def forward(ctx, table, ids, bag_offsets, n_features, offsets, weights,
+                combiner, out_bf16, sink, dense, col_offset, wrap):
+        dim = table.shape[1]
+        batch = (bag_offsets.numel() - 1) // n_features
+        out = None
+        if dense is not None or col_offset:
+            out = torch.empty(
+                batch, col_offset + n_features * dim, device=table.device,
+                dtype=torch.bfloat16 if out_bf16 else torch.float32)
+            n_dense = 0
+            if dense is not None:
+                n_dense = dense.shape[1]
+                out[:, :n_dense] = dense.to(out.dtype)
+            out[:, n_dense:col_offset] = 0
+        out, bag_scale, flat_ids = emb_bag_fwd(
+            table.detach(), ids, bag_offsets, n_features, offsets=offsets,
+            weights=weights, combiner=combiner, out=out,
+            col_offset=col_offset, out_bf16=out_bf16)
+        ctx.sink, ctx.wrap = sink, wrap
+        ctx.dims = (dim, n_features, col_offset, ids.numel())
+        ctx.weights = weights
+        ctx.save_for_backward(bag_offsets, bag_scale, flat_ids)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bag_offsets, bag_scale, flat_ids = ctx.saved_tensors
+        dim, n_features, col_offset, nnz = ctx.dims
+        rows = emb_bag_bwd_rows(grad_out, bag_offsets, bag_scale, dim,
+                                n_features, weights=ctx.weights,
+                                col_offset=col_offset, nnz=nnz)
+        ctx.sink.append(ctx.wrap((flat_ids, rows)))
+        return (None,) * 12
+
+
 def col_reduce_dot(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     """dw[m] = sum_b dy[b] * x[b, m] (fp32 result)."""
     if _on_gpu(x, dy):

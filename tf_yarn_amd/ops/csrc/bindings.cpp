@@ -63,6 +63,19 @@ void emb_fwd_into(torch::Tensor table, torch::Tensor ids,
 void emb_scatter_sum(torch::Tensor table, torch::Tensor ids,
                      torch::Tensor grad, double alpha);
 
+// embedding_bag.hip
+std::vector<torch::Tensor> emb_bag_fwd(
+    torch::Tensor table, torch::Tensor ids, torch::Tensor bag_offsets,
+    int64_t n_features, c10::optional<torch::Tensor> offsets,
+    c10::optional<torch::Tensor> weights, const std::string& combiner,
+    torch::Tensor out, int64_t col_offset);
+torch::Tensor emb_bag_bwd_rows(torch::Tensor grad_out,
+                               torch::Tensor bag_offsets,
+                               torch::Tensor bag_scale, int64_t dim,
+                               int64_t n_features, int64_t nnz,
+                               c10::optional<torch::Tensor> weights,
+                               int64_t col_offset);
+
 // sparse_adagrad.hip
 // one table's side of a stateful sparse update: (rule name, table, state
 // tensors, accumulator, gradient or None, lr, eps, l1, l2); a lazy_adam
@@ -176,6 +189,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("wide_table"), py::arg("ids"),
         py::arg("offsets"), py::arg("dense"), py::arg("out"),
         py::arg("col_offset"));
+  m.def("emb_bag_fwd", &emb_bag_fwd,
+        "Pooled multi-hot lookup from CSR bags into a column slice of out; "
+        "returns (bag_scale, flat_ids)",
+        py::arg("table"), py::arg("ids"), py::arg("bag_offsets"),
+        py::arg("n_features"), py::arg("offsets"), py::arg("weights"),
+        py::arg("combiner"), py::arg("out"), py::arg("col_offset"));
+  m.def("emb_bag_bwd_rows", &emb_bag_bwd_rows,
+        "Pooled gradients -> per-entry update rows [nnz, dim]",
+        py::arg("grad_out"), py::arg("bag_offsets"), py::arg("bag_scale"),
+        py::arg("dim"), py::arg("n_features"), py::arg("nnz"),
+        py::arg("weights"), py::arg("col_offset"));
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
   m.def("emb_bwd_sparse", &emb_bwd_sparse,
