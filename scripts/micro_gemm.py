@@ -211,6 +211,46 @@ def dgrad_fused(sets=6, json_path=None):
     print(json.dumps(res))
 
 
+def wgrad_staging(sets=6, json_path=None):
+    """The split-K weight-gradient kernels at their bench shapes, B =
+    65536, output bf16 as in the step: the register-staged k-loop
+    (regstage=True) against the LDS-DMA staging with transposed LDS reads
+    (regstage=False) in one process, split-K reduce included.  Calls rotate
+    over `sets` input sets.  Also checks the two give equal bits."""
+    import json
+    import tf_yarn_amd.ops._C as C
+    bf16 = torch.bfloat16
+    res = {"batch": B, "sets": sets}
+    for kname, n, m in [("wgrad_nt256", 1024, 432),
+                        ("wgrad_nt256", 512, 1024),
+                        ("wgrad_nt128", 256, 512)]:
+        kernel = getattr(C, kname)
+        dy = [torch.randn(B, n, device="cuda").to(bf16) for _ in range(sets)]
+        x = [torch.randn(B, m, device="cuda").to(bf16) for _ in range(sets)]
+        same = torch.equal(kernel(dy[0], x[0], 0, True, True),
+                           kernel(dy[0], x[0], 0, True, False))
+        gf = 2 * B * n * m / 1e9
+        for name, flag in (("regstage", True), ("glds", False),
+                           ("regstage again", True), ("glds again", False)):
+            med, lo, hi = _timed_windows(
+                lambda i: kernel(dy[i % sets], x[i % sets], 0, True, flag))
+            res[f"{kname} {n}x{m} {name}"] = {
+                "median_us": round(med, 1), "min_us": round(lo, 1),
+                "max_us": round(hi, 1), "tf": round(gf / med * 1e3)}
+            print(f"[{kname} {n:>4}x{m:>4}] {name:15s} {med:7.1f} us "
+                  f"({lo:.1f} .. {hi:.1f})  {gf / med * 1e3:5.0f} TF",
+                  flush=True)
+        res[f"{kname} {n}x{m} equal_bits"] = same
+        print(f"[{kname} {n:>4}x{m:>4}] equal bits: {same}", flush=True)
+        del dy, x
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)),
+                    exist_ok=True)
+        with open(json_path, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
     assert torch.cuda.is_available()
     import sys as _sys
@@ -218,6 +258,9 @@ if __name__ == "__main__":
     if "--dgrad-fused" in _sys.argv:
         dgrad_fused(json_path=_sys.argv[_sys.argv.index("--json") + 1]
                     if "--json" in _sys.argv else None)
+    elif "--wgrad-staging" in _sys.argv:
+        wgrad_staging(json_path=_sys.argv[_sys.argv.index("--json") + 1]
+                      if "--json" in _sys.argv else None)
     elif "--bsweep" in _sys.argv:
         wgrad_b_sweep()
     elif "--fwd" in _sys.argv:

@@ -1523,7 +1523,9 @@ def _custom_wgrad_kernel(dz: torch.Tensor, x: torch.Tensor):
     hipBLASLt.  Measured (micro_gemm.py, B=65536): 256^2 tiles reach
     312/359 TF on the 1024x432 / 512x1024 layers (hipBLASLt in-context ran
     them at ~207 us each); 128^2 tiles win the small 256x512 layer
-    (94 us vs ~142-190)."""
+    (94 us vs ~142-190).  ``MIYARN_WGRAD=regstage`` keeps this choice and
+    makes :func:`_linear_wgrad` ask the kernel for its register-staged
+    k-loop (the control of the LDS-DMA staging; same bits)."""
     if os.environ.get("MIYARN_WGRAD") == "lib":
         return None  # A/B escape hatch: force hipBLASLt
     if not (dz.is_cuda and HAVE_EXT):
@@ -1625,7 +1627,8 @@ def _linear_wgrad(dz: torch.Tensor, x: torch.Tensor,
     kernel = _custom_wgrad_kernel(dz, x)
     if kernel is None:
         return dz.t().matmul(x)
-    dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16)
+    regstage = True if os.environ.get("MIYARN_WGRAD") == "regstage" else None
+    dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16, regstage)
     return dw if dw.dtype == weight.dtype else dw.to(weight.dtype)
 
 

@@ -143,9 +143,12 @@ torch::Tensor bce_head_bwd(torch::Tensor sig, torch::Tensor labels,
 
 // wgrad.hip
 torch::Tensor wgrad_nt128(torch::Tensor dy, torch::Tensor x,
-                          int64_t splitk, bool out_bf16);
+                          int64_t splitk, bool out_bf16,
+                          c10::optional<bool> regstage);
 torch::Tensor wgrad_nt256(torch::Tensor dy, torch::Tensor x,
-                          int64_t splitk, bool out_bf16);
+                          int64_t splitk, bool out_bf16,
+                          c10::optional<bool> regstage);
+py::dict wgrad_glds_layout();
 void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale);
 
 // gemm_bt.hip
@@ -228,13 +231,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("part"), py::arg("out_bf16") = false,
         py::arg("quad_lanes") = 1);
   m.def("wgrad_nt128", &wgrad_nt128,
-        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 128x128 tiles",
+        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 128x128 tiles; "
+        "regstage: True = register-staged k-loop, False = LDS-DMA staging "
+        "with transposed LDS reads, None = this tile's measured default",
         py::arg("dy"), py::arg("x"), py::arg("splitk"),
-        py::arg("out_bf16") = false);
+        py::arg("out_bf16") = false, py::arg("regstage") = py::none());
   m.def("wgrad_nt256", &wgrad_nt256,
-        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 256x256 tiles",
+        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in), 256x256 tiles; "
+        "regstage: True = register-staged k-loop, False = LDS-DMA staging "
+        "with transposed LDS reads, None = this tile's measured default",
         py::arg("dy"), py::arg("x"), py::arg("splitk"),
-        py::arg("out_bf16") = false);
+        py::arg("out_bf16") = false, py::arg("regstage") = py::none());
+  m.def("wgrad_glds_layout", &wgrad_glds_layout,
+        "Constants and image table of the wgrad kernels' LDS-DMA staging");
   m.def("col_reduce_dot", &col_reduce_dot,
         "dw[m] = sum_b dy[b] * x[b,m] (single-logit head wgrad)");
   m.def("col_reduce_dot_sum", &col_reduce_dot_sum,
