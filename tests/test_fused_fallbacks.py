@@ -104,6 +104,55 @@ def test_linear_bias_relu_head_cpu_matches_the_two_modules():
         assert torch.equal(a, c)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16],
+                         ids=["f32", "bf16"])
+def test_linear_bias_relu_head_one_layer_node(dtype, monkeypatch):
+    """``linear_bias_relu_head`` is the one-layer ``MLPHeadFn``: at
+    8 x 12 -> 8 -> 1 output and all five gradients equal ScalarHeadFn over
+    LinearBiasReLU.  With an input that needs no gradient the backward
+    skips ``dz @ W`` (one matmul fewer) and the other four gradients are
+    the same."""
+    gen = torch.Generator().manual_seed(7)
+    vals = [torch.randn(8, 12, generator=gen), torch.randn(8, 12, generator=gen),
+            torch.randn(8, generator=gen), torch.randn(8, generator=gen),
+            torch.randn(1, generator=gen)]
+    g = torch.randn(8, generator=gen).to(dtype)
+    real_matmul = torch.Tensor.matmul
+    calls = []
+
+    def counting_matmul(self, other):
+        calls.append(1)
+        return real_matmul(self, other)
+
+    def run(fused, x_grad):
+        x, w, bias, wh, bh = [v.clone().to(dtype).requires_grad_(True)
+                              for v in vals]  # fresh leaves every run
+        x.requires_grad_(x_grad)
+        if fused:
+            out = ops.linear_bias_relu_head(x, w, bias, wh, bh)
+        else:
+            out = ops.ScalarHeadFn.apply(ops.linear_bias_relu(x, w, bias),
+                                         wh, bh)
+        del calls[:]
+        with monkeypatch.context() as m:
+            m.setattr(torch.Tensor, "matmul", counting_matmul)
+            out.backward(g)
+        grads = [t.grad for t in (x, w, bias, wh, bh)]
+        return [out.detach()] + grads, len(calls)
+
+    want, _ = run(False, True)
+    got, n_dx = run(True, True)
+    assert all(t is not None for t in want + got)
+    assert not any(a is c for a, c in zip(got, want))
+    for a, c in zip(got, want):
+        assert a.dtype == c.dtype and torch.equal(a, c)
+    got_no_dx, n_no_dx = run(True, False)
+    assert got_no_dx[1] is None
+    assert n_no_dx == n_dx - 1
+    for a, c in zip(got_no_dx[:1] + got_no_dx[2:], want[:1] + want[2:]):
+        assert torch.equal(a, c)
+
+
 def _train_two_steps(monkeypatch, switch):
     from tf_yarn_amd.models.wide_deep import WideAndDeep
     from tf_yarn_amd.ops.optim import FusedSGD

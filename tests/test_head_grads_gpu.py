@@ -153,7 +153,7 @@ _B = 4160  # 65 k-steps of the custom wgrad; 130 partial rows at 256 columns
 
 
 def _head_fn_grads():
-    """LinearBiasReLUHeadFn at 4160 x 64 -> 256 -> 1.  |z| <= 2*64 + 2, so y
+    """linear_bias_relu_head at 4160 x 64 -> 256 -> 1.  |z| <= 2*64 + 2, so y
     is an integer bf16 holds, and every gradient is an exact integer sum
     (worst: dw_head, 2 * 130 * 4160 < 2^24)."""
     exact_ints.assert_exact(2, 130, _B)

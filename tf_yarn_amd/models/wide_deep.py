@@ -876,38 +876,34 @@ class WideAndDeep(nn.Module):
         """``head(mlp(deep_in))``.  On the GPU in bf16 the last hidden
         layer and the head run as one autograd node whose backward never
         materialises the head's ``[B, width]`` input gradient
-        (``ops.LinearBiasReLUHeadFn``; same kernels and bits otherwise).
+        (``ops.linear_bias_relu_head``; same kernels and bits otherwise).
         MIYARN_FUSED_HEAD_BWD=0 keeps the two modules apart.  At a batch
         that is a multiple of 256, a tower with a hidden layer whose dgrad
-        shape is routed to ``ops.dgrad_drelu`` runs as ``ops.MLPHeadFn``."""
-        n = len(self.mlp)
-        last = self.mlp[n - 1] if n else None
+        shape is routed to ``ops.dgrad_drelu`` runs as ``ops.MLPHeadFn``
+        over all its layers (MIYARN_FUSED_DGRAD=0 keeps the per-layer
+        nodes)."""
+        bf16 = torch.bfloat16
         head = self.head
-        if not (isinstance(last, FusedLinearReLU) and deep_in.is_cuda
-                and ops.HAVE_EXT and deep_in.dim() == 2
-                and deep_in.dtype == torch.bfloat16
-                and last.weight.dtype == torch.bfloat16
-                and last.bias.dtype == torch.bfloat16
-                and head.weight.dtype == torch.bfloat16
-                and head.bias.dtype == torch.bfloat16
-                and last.weight.shape[0] % 4 == 0
+        # which layers are bf16 FusedLinearReLU: the fused head needs the
+        # last one, the whole-tower node all of them
+        fused = [isinstance(m, FusedLinearReLU) and m.weight.dtype == bf16
+                 and m.bias.dtype == bf16 for m in self.mlp]
+        if not (fused and fused[-1] and deep_in.is_cuda and ops.HAVE_EXT
+                and deep_in.dim() == 2 and deep_in.dtype == bf16
+                and head.weight.dtype == bf16 and head.bias.dtype == bf16
+                and self.mlp[-1].weight.shape[0] % 4 == 0
                 and ops.fused_head_bwd_enabled()):
             return head(self.mlp(deep_in))
-        # The whole tower as one node where a hidden layer's dgrad is
-        # routed to the kernel that applies the ReLU mask of the layer
-        # below in its epilogue (ops.MLPHeadFn; MIYARN_FUSED_DGRAD=0
-        # keeps the per-layer nodes).
-        if all(isinstance(m, FusedLinearReLU)
-               and m.weight.dtype == torch.bfloat16
-               and m.bias.dtype == torch.bfloat16 for m in self.mlp):
+        if all(fused):
             weights = [m.weight for m in self.mlp]
             if ops.mlp_head_routed(deep_in, weights):
                 return ops.mlp_bias_relu_head(
                     deep_in, weights, [m.bias for m in self.mlp],
                     head.weight, head.bias)
+        *leading, last = self.mlp
         h = deep_in
-        for i in range(n - 1):
-            h = self.mlp[i](h)
+        for m in leading:
+            h = m(h)
         return ops.linear_bias_relu_head(h, last.weight, last.bias,
                                          head.weight, head.bias)
 

@@ -1412,6 +1412,18 @@ def gemm_bt(a: torch.Tensor, b: torch.Tensor,
     return out.to(a.dtype)
 
 
+def _head_fwd(x: torch.Tensor, weight: torch.Tensor,
+              bias: torch.Tensor) -> torch.Tensor:
+    """A single-logit head's forward, ``x @ weight + bias``: the
+    :func:`row_dot` kernel at the widths it takes, else the library."""
+    if _on_gpu(x, weight) and x.size(1) % 4 == 0 \
+            and x.size(1) <= 512 and bias.numel() == 1:
+        _require_ext()
+        return _C.row_dot(x.contiguous(), weight.contiguous(),
+                          bias.reshape(1))
+    return x @ weight + bias
+
+
 class ScalarHeadFn(torch.autograd.Function):
     """y[b] = x[b].w + bias for a single-logit head; the wgrad runs as a
     streaming column reduction instead of hipBLASLt's M=1 GEMM
@@ -1420,12 +1432,7 @@ class ScalarHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
-        if _on_gpu(x, weight) and x.size(1) % 4 == 0 \
-                and x.size(1) <= 512 and bias.numel() == 1:
-            _require_ext()
-            return _C.row_dot(x.contiguous(), weight.contiguous(),
-                              bias.reshape(1))
-        return x @ weight + bias
+        return _head_fwd(x, weight, bias)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1486,6 +1493,24 @@ def bce_head_loss(deep: torch.Tensor, wide: torch.Tensor,
     return BCEHeadFn.apply(deep, wide, dhead, labels).mean()
 
 
+def _relu_bwd_db(dy: torch.Tensor, y: torch.Tensor):
+    """``(dz, dbias)`` of a bias+ReLU from its output gradient and output;
+    the only place that chooses between the fused kernel and
+    ``bias_relu_bwd`` + ``sum``.  ``dbias`` has ``dy``'s dtype (``.to`` of
+    a tensor already in it returns that tensor)."""
+    dy = dy.contiguous()
+    if dy.is_cuda and HAVE_EXT and y.size(-1) % 4 == 0 \
+            and y.size(-1) <= 8192:
+        # v3 fused kernel: atomic-free per-block column partials +
+        # one tiny reduce (earlier atomic/LDS variants measured
+        # slower than the separate path; see micro_elementwise.py).
+        dz, dbias = _C.bias_relu_bwd_db(
+            dy, y.contiguous(), dy.dtype == torch.bfloat16)
+        return dz, dbias.to(dy.dtype)
+    dz = bias_relu_bwd(dy, y)
+    return dz, dz.sum(dim=tuple(range(dz.dim() - 1)))
+
+
 class BiasReLU(torch.autograd.Function):
     """Autograd wrapper for the fused bias+ReLU epilogue (backward fuses
     the dbias reduction into the dx kernel on GPU)."""
@@ -1499,19 +1524,7 @@ class BiasReLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        if dy.is_cuda and HAVE_EXT and y.size(-1) % 4 == 0 \
-                and y.size(-1) <= 8192:
-            # v3 fused kernel: atomic-free per-block column partials +
-            # one tiny reduce (earlier atomic/LDS variants measured
-            # slower than the separate path; see micro_elementwise.py).
-            dx, dbias = _C.bias_relu_bwd_db(
-                dy.contiguous(), y.contiguous(),
-                dy.dtype == torch.bfloat16)
-            return dx, dbias.to(dy.dtype)
-        dx = bias_relu_bwd(dy.contiguous(), y)
-        dims = tuple(range(dx.dim() - 1))
-        dbias = dx.sum(dim=dims)
-        return dx, dbias
+        return _relu_bwd_db(dy, y)
 
 
 def bias_relu(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -1646,16 +1659,7 @@ class LinearBiasReLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        if dy.is_cuda and HAVE_EXT and y.size(-1) % 4 == 0 \
-                and y.size(-1) <= 8192:
-            dz, dbias = _C.bias_relu_bwd_db(
-                dy, y.contiguous(), dy.dtype == torch.bfloat16)
-            if dbias.dtype != dy.dtype:
-                dbias = dbias.to(dy.dtype)
-        else:
-            dz = bias_relu_bwd(dy, y)
-            dbias = dz.sum(dim=tuple(range(dz.dim() - 1)))
+        dz, dbias = _relu_bwd_db(dy, y)
         dx = dz.matmul(weight)
         return dx, _linear_wgrad(dz, x, weight), dbias
 
@@ -1719,49 +1723,17 @@ def head_relu_bwd_grads(dl: torch.Tensor, w_head: torch.Tensor,
     return dz, dbias, dw_head, db_head
 
 
-class LinearBiasReLUHeadFn(torch.autograd.Function):
-    """``relu(x @ w.T + bias) . w_head + b_head``: the last hidden layer
-    and the single-logit head as ONE autograd node, so that backward goes
-    from the logit gradient straight to the layer's ``dz``
-    (:func:`head_relu_bwd_db`) instead of writing and re-reading the head's
-    ``[B, width]`` input gradient.  Forward is :class:`LinearBiasReLU`'s
-    followed by :class:`ScalarHeadFn`'s, backward computes what the two
-    nodes computed, kernel for kernel, except for that product."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, w_head, b_head):
-        y = _linear_bias_relu_fwd(x, weight, bias)
-        ctx.save_for_backward(x, weight, y, w_head)
-        if _on_gpu(y, w_head) and y.size(1) % 4 == 0 \
-                and y.size(1) <= 512 and b_head.numel() == 1:
-            _require_ext()
-            return _C.row_dot(y.contiguous(), w_head.contiguous(),
-                              b_head.reshape(1))
-        return y @ w_head + b_head
-
-    @staticmethod
-    def backward(ctx, dl):
-        x, weight, y, w_head = ctx.saved_tensors
-        dl = dl.contiguous()
-        dw_head = db_head = None
-        if ctx.needs_input_grad[3] and ctx.needs_input_grad[4] \
-                and _on_gpu(dl, y) and fused_head_grads_enabled():
-            dz, dbias, dw_head, db_head = head_relu_bwd_grads(dl, w_head, y)
-        else:
-            if ctx.needs_input_grad[3]:
-                dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
-            if ctx.needs_input_grad[4]:
-                db_head = dl.sum().reshape(1).to(w_head.dtype)
-            dz, dbias = head_relu_bwd_db(dl, w_head, y)
-        dx = dz.matmul(weight)
-        dw = _linear_wgrad(dz, x, weight)
-        return dx, dw, dbias, dw_head, db_head
-
-
 def linear_bias_relu_head(x: torch.Tensor, weight: torch.Tensor,
                           bias: torch.Tensor, w_head: torch.Tensor,
                           b_head: torch.Tensor) -> torch.Tensor:
-    return LinearBiasReLUHeadFn.apply(x, weight, bias, w_head, b_head)
+    """``relu(x @ weight.T + bias) . w_head + b_head``: the last hidden
+    layer and the single-logit head as ONE autograd node
+    (:class:`MLPHeadFn` with one layer), so that backward goes from the
+    logit gradient straight to the layer's ``dz`` instead of writing and
+    re-reading the head's ``[B, width]`` input gradient.  Kernel for
+    kernel what :class:`LinearBiasReLU` and :class:`ScalarHeadFn` run,
+    except for that product."""
+    return MLPHeadFn.apply(x, w_head, b_head, weight, bias)
 
 
 # ---- dgrad + ReLU backward + dbias in one kernel; the tower as one node ----
@@ -1810,24 +1782,28 @@ def dgrad_drelu(dz_next: torch.Tensor, weight: torch.Tensor,
     return _relu_bwd_db(dz_next.matmul(weight), y)
 
 
-def _relu_bwd_db(dy: torch.Tensor, y: torch.Tensor):
-    """``(dz, dbias)`` from a layer's output gradient, exactly as
-    :class:`LinearBiasReLU`'s backward computes them."""
-    dy = dy.contiguous()
-    if dy.is_cuda and HAVE_EXT and y.size(-1) % 4 == 0 \
-            and y.size(-1) <= 8192:
-        dz, dbias = _C.bias_relu_bwd_db(
-            dy, y.contiguous(), dy.dtype == torch.bfloat16)
-        if dbias.dtype != dy.dtype:
-            dbias = dbias.to(dy.dtype)
-        return dz, dbias
-    dz = bias_relu_bwd(dy, y)
-    return dz, dz.sum(dim=tuple(range(dz.dim() - 1)))
+def _head_relu_bwd(dl: torch.Tensor, w_head: torch.Tensor, y: torch.Tensor,
+                   need_dw_head: bool, need_db_head: bool):
+    """``(dz, dbias, dw_head, db_head)`` of "last hidden layer's ReLU +
+    single-logit head": :func:`head_relu_bwd_grads` when both head
+    gradients are wanted on the GPU and MIYARN_FUSED_HEAD_GRADS is on, else
+    :func:`head_relu_bwd_db` and the separate head gradients asked for."""
+    if need_dw_head and need_db_head and _on_gpu(dl, y) \
+            and fused_head_grads_enabled():
+        return head_relu_bwd_grads(dl, w_head, y)
+    dw_head = db_head = None
+    if need_dw_head:
+        dw_head = col_reduce_dot(y, dl).to(w_head.dtype)
+    if need_db_head:
+        db_head = dl.sum().reshape(1).to(w_head.dtype)
+    dz, dbias = head_relu_bwd_db(dl, w_head, y)
+    return dz, dbias, dw_head, db_head
 
 
 class MLPHeadFn(torch.autograd.Function):
-    """The whole deep tower, ``n`` bias+ReLU layers and the single-logit
-    head, as ONE autograd node.  The ReLU mask of layer ``l`` needs
+    """``n`` bias+ReLU layers and the single-logit head as ONE autograd
+    node: the whole deep tower, or with ``n = 1`` the last hidden layer and
+    the head (:func:`linear_bias_relu_head`).  The ReLU mask of layer ``l`` needs
     ``y_l``, which per-layer nodes hand to layer ``l``'s backward; with one
     node, layer ``l+1``'s dgrad can apply it in its own epilogue
     (:func:`dgrad_drelu`).  Forward runs the per-layer nodes' kernels and
@@ -1848,12 +1824,7 @@ class MLPHeadFn(torch.autograd.Function):
             ys.append(h)
         ctx.n_layers = n
         ctx.save_for_backward(x, w_head, *weights, *ys)
-        if _on_gpu(h, w_head) and h.size(1) % 4 == 0 \
-                and h.size(1) <= 512 and b_head.numel() == 1:
-            _require_ext()
-            return _C.row_dot(h.contiguous(), w_head.contiguous(),
-                              b_head.reshape(1))
-        return h @ w_head + b_head
+        return _head_fwd(h, w_head, b_head)
 
     @staticmethod
     def backward(ctx, dl):
@@ -1861,18 +1832,9 @@ class MLPHeadFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, w_head = saved[0], saved[1]
         weights, ys = saved[2:2 + n], saved[2 + n:]
-        dl = dl.contiguous()
-        dw_head = db_head = None
-        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] \
-                and _on_gpu(dl, ys[-1]) and fused_head_grads_enabled():
-            dz, dbias, dw_head, db_head = head_relu_bwd_grads(
-                dl, w_head, ys[-1])
-        else:
-            if ctx.needs_input_grad[1]:
-                dw_head = col_reduce_dot(ys[-1], dl).to(w_head.dtype)
-            if ctx.needs_input_grad[2]:
-                db_head = dl.sum().reshape(1).to(w_head.dtype)
-            dz, dbias = head_relu_bwd_db(dl, w_head, ys[-1])
+        dz, dbias, dw_head, db_head = _head_relu_bwd(
+            dl.contiguous(), w_head, ys[-1], ctx.needs_input_grad[1],
+            ctx.needs_input_grad[2])
         dws = [None] * n
         dbs = [None] * n
         fused = fused_dgrad_enabled()

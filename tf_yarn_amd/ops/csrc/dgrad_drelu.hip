@@ -9,12 +9,12 @@
 // memory.  hipBLASLt has no DReLU+bias-gradient epilogue, so this is the
 // one GEMM of the step the library cannot fuse.
 //
-// Operands.  dz_next [M, K] is K-major and stages linearly (gemm_bt's A
-// operand, lds_off_linear).  w [K, N] is the weight as stored: its rows
-// are the reduction index and N is contiguous, the shape of wgrad_kernel's
-// x operand, so it takes that staging: coalesced 16 B row loads, packed
-// b64 transposed LDS writes under lds_off, columns masked at the ragged
-// tile.  No W^T copy is made.
+// Operands.  dz_next [M, K] is K-major and takes mfma_tile.h's K-major
+// staging (gemm_bt's A operand).  w [K, N] is the weight as stored: its
+// rows are the reduction index and N is contiguous, the shape of
+// wgrad_kernel's x operand, so it takes the strided-k staging, columns
+// masked at the ragged tile.  No W^T copy is made.  Tile map and k-step
+// are the header's too.
 //
 // The MFMA takes the w fragment FIRST: D's row index (four consecutive
 // per lane) is then n and its column index (lane & 15) is m, so a lane
@@ -49,11 +49,6 @@ namespace {
 // kernel stays written over TILE as wgrad_kernel is.
 #define DD_TILE 128
 
-union DdU16x4 {
-  unsigned short u[4];
-  unsigned long long ll;
-};
-
 // byte offset of bf16 [row][col] in the parked half tile of PW columns:
 // 16 B chunk index XOR the row (row pair when two rows share 256 B)
 template <int PW>
@@ -84,17 +79,7 @@ void dgrad_drelu_kernel(const unsigned short* __restrict__ A,  // dz_next
   const int tiles_n = (N + TILE - 1) / TILE;
   const int tiles_m = static_cast<int>(M / TILE);
   int tile_m, tile_n;
-  if ((tiles_m & 7) == 0) {
-    // gemm_bt's XCD-grouped map: the column tiles of one row block land
-    // on one XCD and share their rows of dz_next through its L2
-    const int c = blockIdx.x & 7;
-    const int q = blockIdx.x >> 3;
-    tile_n = q % tiles_n;
-    tile_m = c + 8 * (q / tiles_n);
-  } else {
-    tile_m = blockIdx.x / tiles_n;
-    tile_n = blockIdx.x - tile_m * tiles_n;
-  }
+  xcd_tile_map(tiles_m, tiles_n, tile_m, tile_n);  // shares dz_next's rows
   const int64_t m0 = (int64_t)tile_m * TILE;
   const int n0 = tile_n * TILE;
 
@@ -109,37 +94,25 @@ void dgrad_drelu_kernel(const unsigned short* __restrict__ A,  // dz_next
   const int wm = (wave >> 1) * 64;         // M-quadrants of 64
   const int wn = (wave & 1) * (TILE / 2);  // 2 N-halves
 
-  // dz_next staging: row = t >> 1, k seg = (t & 1) * 32
+  // dz_next: K-major staging; w: strided-k staging (mfma_tile.h)
   const int st_r = tid >> 1;
   const int st_k = (tid & 1) * 32;
-  // w staging: thread = 4 k-rows x 8 cols
   const int st_kg = (tid / SC) * 4;
   const int st_c = (tid % SC) * 8;
   const bool w_col_ok = (n0 + st_c) < N;  // N % 16 == 0: whole octs
 
   mfma_f32x4 acc[FI][FJ];
-#pragma unroll
-  for (int i = 0; i < FI; ++i)
-#pragma unroll
-    for (int j = 0; j < FJ; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  const int a_row = lane & 15;
-  const int a_k = (lane >> 4) * 8;
+  zero_acc(acc);
 
   bf16x8 ra[4], rw[4];
 
   auto load_step = [&](int k0) {
-    const unsigned short* pa = A + (m0 + st_r) * (int64_t)K + k0 + st_k;
-    // K % 16 == 0: whole 8-element vectors are either in or out
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      ra[c] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (k0 + st_k + c * 8 + 8 <= K)
-        ra[c] = *reinterpret_cast<const bf16x8*>(pa + c * 8);
-    }
-    // real branches: a masked lane must not issue the load at all.  The
-    // thread's four k-rows start at a multiple of 4, so they are all in
-    // or all out.
+    stage_kmajor_load(ra, A + (m0 + st_r) * (int64_t)K + k0 + st_k, true,
+                      k0 + st_k, K);
+    // stage_strided_load, written out: through the header's function this
+    // kernel takes 166-168 VGPRs instead of 164, and its 512 -> 1024
+    // routing rests on that count.  Real branches: a masked lane must not
+    // issue the load at all; the four k-rows are all in or all out.
     const bool w_ok = w_col_ok && (k0 + st_kg) < K;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
@@ -150,23 +123,10 @@ void dgrad_drelu_kernel(const unsigned short* __restrict__ A,  // dz_next
     }
   };
 
-  auto write_step = [&] {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      *reinterpret_cast<bf16x8*>(aT + lds_off_linear(st_r, st_k + c * 8)) =
-          ra[c];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      DdU16x4 p{{rw[0][j], rw[1][j], rw[2][j], rw[3][j]}};
-      *reinterpret_cast<unsigned long long*>(
-          wT + lds_off(st_c + j, st_kg)) = p.ll;
-    }
-  };
-
-  // fragment (i, j): row wm + i*16 + (lane & 15), columns
-  // wn + j*16 + (lane >> 4)*4 + 0..3
-  const int e_m = lane & 15;
-  const int e_n = (lane >> 4) * 4;
+  // fragment (i, j): row wm + i*16 + f_col, columns
+  // wn + j*16 + f_row4 + 0..3
+  int f_col, f_row4;
+  frag_pos(lane, f_col, f_row4);
   // walk: one oct of columns, rows w_row + s * RPS
   const int w_row = tid / OPR;
   const int w_oct = tid - w_row * OPR;
@@ -188,27 +148,13 @@ void dgrad_drelu_kernel(const unsigned short* __restrict__ A,  // dz_next
 
   load_step(0);
   for (int k0 = 0; k0 < K; k0 += DD_BK) {
-    write_step();
+    stage_kmajor_write(aT, ra, st_r, st_k);
+    stage_strided_write(wT, rw, st_c, st_kg);
     __syncthreads();
     if (k0 + DD_BK < K) load_step(k0 + DD_BK);  // in flight under MFMA
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      mfma_bf16x8 a[FI], b[FJ];
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-        a[i] = *reinterpret_cast<const mfma_bf16x8*>(
-            aT + lds_off_linear(wm + i * 16 + a_row, kh * 32 + a_k));
-#pragma unroll
-      for (int j = 0; j < FJ; ++j)
-        b[j] = *reinterpret_cast<const mfma_bf16x8*>(
-            wT + lds_off(wn + j * 16 + a_row, kh * 32 + a_k));
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < FJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              b[j], a[i], acc[i][j], 0, 0, 0);
-    }
+    // the w fragment goes first (header comment)
+    mfma_kstep<FI, FJ, lds_off_linear, lds_off, true>(acc, aT, wT, wm, wn,
+                                                      lane);
     __syncthreads();
   }
 
@@ -228,10 +174,10 @@ void dgrad_drelu_kernel(const unsigned short* __restrict__ A,  // dz_next
       for (int i = 0; i < FI; ++i)
 #pragma unroll
         for (int j = 0; j < FJ; ++j) {
-          DdU16x4 v{{f32_to_bf16(acc[i][j][0]), f32_to_bf16(acc[i][j][1]),
-                     f32_to_bf16(acc[i][j][2]), f32_to_bf16(acc[i][j][3])}};
+          U16x4 v{{f32_to_bf16(acc[i][j][0]), f32_to_bf16(acc[i][j][1]),
+                   f32_to_bf16(acc[i][j][2]), f32_to_bf16(acc[i][j][3])}};
           *reinterpret_cast<unsigned long long*>(
-              lds_raw + park_off<PW>(wm + i * 16 + e_m, j * 16 + e_n)) =
+              lds_raw + park_off<PW>(wm + i * 16 + f_col, j * 16 + f_row4)) =
               v.ll;
         }
     }

@@ -61,11 +61,6 @@ namespace {
 
 #define WG_BK 64
 
-union U16x4 {
-  unsigned short u[4];
-  unsigned long long ll;
-};
-
 // LDS-DMA staging (GLDS = true) constants; mirrored by
 // tests/wgrad_image.py through wgrad_glds_layout().
 constexpr int WG_IMG_COLS = 128;                 // columns of one image
@@ -113,6 +108,11 @@ void wgrad_kernel(const unsigned short* __restrict__ dy,
   const int wn = (wave >> 1) * 64;          // N-quadrants of 64
   const int wm = (wave & 1) * (TILE / 2);   // 2 M-halves
 
+  // The zeroing here and the fragment coordinates of the epilogue are
+  // written out, not taken from mfma_tile.h (zero_acc, frag_pos): both
+  // k-loops share them, and through the header's functions the LDS-DMA
+  // kernels come out with another register allocation (4 more AGPRs at
+  // TILE=128).  Written out, their instruction streams do not move.
   mfma_f32x4 acc[FN][FM];
 #pragma unroll
   for (int i = 0; i < FN; ++i)
@@ -243,96 +243,52 @@ void wgrad_kernel(const unsigned short* __restrict__ dy,
     unsigned char* dyT = lds_raw;              // [TILE n][64 k] swizzled
     unsigned char* xT = lds_raw + TILE * 128;  // [TILE m][64 k]
 
-    // staging map (per tile [64 k][TILE cols]): thread = 4 k-rows x 8 cols
-    // (4 x 16 B coalesced loads -> 8 packed b64 transposed LDS writes)
+    // both operands take mfma_tile.h's strided-k staging.  dy needs no
+    // mask (N % TILE == 0, whole 64-row k-steps).  x is masked by whole
+    // octs: with M % 8 == 0 and st_c % 8 == 0 an oct's two halves are in
+    // or out together.  The 16 B loads need 16 B-aligned row starts, as the
+    // LDS-DMA branch does: N and M are multiples of 8 and a contiguous
+    // tensor starts on an allocation boundary.
     const int st_kg = (tid / SC) * 4;
     const int st_c = (tid % SC) * 8;
-
-    const int a_row = lane & 15;
-    const int a_k = (lane >> 4) * 8;
-    const bool m_edge = (m0 + TILE) > M;
-    const bool in0 = !m_edge || (m0 + st_c + 4) <= M;
-    const bool in1 = !m_edge || (m0 + st_c + 8) <= M;
+    const bool x_col_ok = (m0 + st_c) < M;
 
     // T14 split (guide G15): issue the NEXT step's global loads before this
     // step's MFMA phase so HBM latency hides under compute; the register
     // tile is written to LDS after the barrier.
-    bf16x4 rdy[4][2], rx[4][2];
+    bf16x8 rdy[4], rx[4];
 
     auto load_step = [&](int64_t k0) {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const unsigned short* src =
-            dy + (k0 + st_kg + rr) * (int64_t)N + n0 + st_c;
-        rdy[rr][0] = reinterpret_cast<const bf16x4*>(src)[0];
-        rdy[rr][1] = reinterpret_cast<const bf16x4*>(src)[1];
-        const unsigned short* srcx =
-            x + (k0 + st_kg + rr) * (int64_t)M + m0 + st_c;
-        // real branches (EXEC-masked loads): an out-of-range lane must not
-        // issue the load at all (last row would read past the tensor)
-        rx[rr][0] = bf16x4{0, 0, 0, 0};
-        rx[rr][1] = bf16x4{0, 0, 0, 0};
-        if (in0) rx[rr][0] = reinterpret_cast<const bf16x4*>(srcx)[0];
-        if (in1) rx[rr][1] = reinterpret_cast<const bf16x4*>(srcx)[1];
-      }
-    };
-
-    auto write_step = [&] {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          U16x4 p{{rdy[0][h][j], rdy[1][h][j], rdy[2][h][j], rdy[3][h][j]}};
-          *reinterpret_cast<unsigned long long*>(
-              dyT + lds_off(st_c + h * 4 + j, st_kg)) = p.ll;
-          U16x4 q{{rx[0][h][j], rx[1][h][j], rx[2][h][j], rx[3][h][j]}};
-          *reinterpret_cast<unsigned long long*>(
-              xT + lds_off(st_c + h * 4 + j, st_kg)) = q.ll;
-        }
+      const int64_t kr = k0 + st_kg;
+      stage_strided_load(rdy, dy + kr * N + n0 + st_c, N, true);
+      stage_strided_load(rx, x + kr * M + m0 + st_c, M, x_col_ok);
     };
 
     load_step(k_begin);
     for (int64_t k0 = k_begin; k0 < k_end; k0 += WG_BK) {
-      write_step();
+      stage_strided_write(dyT, rdy, st_c, st_kg);
+      stage_strided_write(xT, rx, st_c, st_kg);
       __syncthreads();
       if (k0 + WG_BK < k_end)
         load_step(k0 + WG_BK);  // in flight under the MFMA phase
-      // ---- MFMA: FN x FM fragments x 2 k-halves ---------------------------
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        mfma_bf16x8 a[FN], b[FM];
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-          a[i] = *reinterpret_cast<const mfma_bf16x8*>(
-              dyT + lds_off(wn + i * 16 + a_row, kh * 32 + a_k));
-#pragma unroll
-        for (int j = 0; j < FM; ++j)
-          b[j] = *reinterpret_cast<const mfma_bf16x8*>(
-              xT + lds_off(wm + j * 16 + a_row, kh * 32 + a_k));
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a[i], b[j], acc[i][j], 0, 0, 0);
-      }
+      mfma_kstep<FN, FM, lds_off, lds_off, false>(acc, dyT, xT, wn, wm, lane);
       __syncthreads();
     }
   }
 
   // ---- epilogue: fp32 partial slab (column-masked) ----------------------
   float* out = part + (int64_t)blockIdx.x * N * M;
-  const int c_col = lane & 15;
-  const int c_row = (lane >> 4) * 4;
+  const int f_col = lane & 15;         // frag_pos, written out (see above)
+  const int f_row4 = (lane >> 4) * 4;
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
-      const int col = m0 + wm + j * 16 + c_col;
+      const int col = m0 + wm + j * 16 + f_col;
       if (col >= M) continue;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = n0 + wn + i * 16 + c_row + r;
+        const int row = n0 + wn + i * 16 + f_row4 + r;
         out[(int64_t)row * M + col] = acc[i][j][r];
       }
     }
