@@ -516,24 +516,41 @@ class _ModuleRef:
             alpha=ALPHA)
 
 
-def _module_fwd_bwd(emb, ref, batch, perm_stream):
+class _CountedPermutation:
+    """``ops.binned_permutation`` with every permutation it returned."""
+
+    def __init__(self, monkeypatch):
+        self.built, self._fn = [], ops.binned_permutation
+        monkeypatch.setattr(ops, "binned_permutation", self)
+
+    def __call__(self, *args):
+        self.built.append(self._fn(*args))
+        return self.built[-1]
+
+
+def _module_fwd_bwd(emb, ref, batch, perm_stream, counted):
     """Forward (checked), backward with the batch's integer gradients;
-    returns the address of the flat ids the sinks now hold."""
+    returns the record that backward left."""
     ids, g_buf, g_wide = batch
     buf = torch.zeros(MOD_B, len(MOD_TABLES) * DIM, device="cuda")
+    n_built = len(counted.built)
     out, wide = emb(ids.cuda(), buf, 0)
     # the permutation was started in forward, on the side stream or inline
-    key, _, event = emb._pending_perm
-    assert (event is not None) == perm_stream
+    assert len(counted.built) == n_built + 1
     want_out, want_wide = ref.forward(ids)
     assert torch.equal(out.detach().cpu(), want_out)
     assert torch.equal(wide.detach().cpu(), want_wide)
-    n_sunk = len(emb._deep_sink)
+    n_pending = len(emb.pending_grads())
     torch.autograd.backward([out, wide],
                             [g_buf.float().cuda(), g_wide.float().cuda()])
-    assert len(emb._deep_sink) == len(emb._wide_sink) == n_sunk + 1
-    assert emb._deep_sink[-1][0].data_ptr() == key
-    return key
+    assert len(emb.pending_grads()) == n_pending + 1
+    record = emb.pending_grads()[-1]
+    # ... and backward moved that very permutation into its record
+    perm, event = record.perm
+    assert perm is counted.built[-1] and len(counted.built) == n_built + 1
+    assert (event is not None) == perm_stream
+    assert not record.raw_ids
+    return record
 
 
 @requires_gpu
@@ -548,16 +565,19 @@ def test_module_binned_path(monkeypatch, apply_stream, perm_stream, law,
                             steps):
     """``ShardedCriteoEmbeddings`` at world 1 with the binned scatter
     forced on: the permutation built during forward (side stream with its
-    event, or inline) is handed to both kernels by the address of the ids,
-    and the float64 ``index_add_`` of both tables comes back exactly.
+    event, or inline) travels in the record of its own backward to both
+    kernels, and the float64 ``index_add_`` of both tables comes back
+    exactly.
     lr 0.5 at world 1 gives alpha = -0.5, and backward hands the integer
     gradients to the sinks unscaled, so nothing needs other values.
     apply_on_stream: ``apply_sparse_updates(lr, stream=S)`` runs both
     kernels on the caller's stream, a third stream for a permutation built
     on the side stream and a second for one built inline.
     two_steps: the second forward's ids may land on the freed address of
-    the first's.  two_forwards_one_apply: only the second forward still
-    has a pending permutation; the first's is built on demand."""
+    the first's, which nothing may depend on.  two_forwards_one_apply:
+    both records carry the permutation of their own forward, so
+    ``ops.binned_permutation`` runs exactly twice, both times in forward,
+    and the apply builds none."""
     from tf_yarn_amd.models.sharded_embedding import \
         ShardedCriteoEmbeddings
     monkeypatch.setenv("MIYARN_BINNED_SCATTER", "1")
@@ -572,6 +592,7 @@ def test_module_binned_path(monkeypatch, apply_stream, perm_stream, law,
         emb.weight.copy_(deep.float())
         emb.wide_weight.copy_(wide.float())
     ref = _ModuleRef(deep, wide)
+    counted = _CountedPermutation(monkeypatch)
     batches = [_module_batch(law, gen) for _ in range(2)]
     assert not torch.equal(batches[0][0], batches[1][0])
     # worst case: both batches hit one row MOD_B times each
@@ -586,8 +607,7 @@ def test_module_binned_path(monkeypatch, apply_stream, perm_stream, law,
 
     def check(what):
         torch.cuda.synchronize()
-        assert emb._pending_perm is None
-        assert not emb._deep_sink and not emb._wide_sink
+        assert not emb.pending_grads()
         for got, want in ((emb.weight, ref.deep), (emb.wide_weight,
                                                    ref.wide)):
             got, want = got.detach().cpu(), want.float()
@@ -596,43 +616,65 @@ def test_module_binned_path(monkeypatch, apply_stream, perm_stream, law,
                 f"{what}: rows {bad[:8].tolist()} of {tuple(got.shape)}"
 
     if steps == "two_forwards_one_apply":
-        first = _module_fwd_bwd(emb, ref, batches[0], perm_stream)
-        second = _module_fwd_bwd(emb, ref, batches[1], perm_stream)
-        assert first != second and emb._pending_perm[0] == second
+        first = _module_fwd_bwd(emb, ref, batches[0], perm_stream, counted)
+        second = _module_fwd_bwd(emb, ref, batches[1], perm_stream, counted)
+        pending = emb.pending_grads()
+        assert len(pending) == 2
+        assert pending[0] is first and pending[1] is second
+        assert first.perm[0] is not second.perm[0]
+        assert len(counted.built) == 2
         apply()
+        assert len(counted.built) == 2  # none at apply
         for batch in batches:
             ref.update(*batch)
         check("two forwards, one apply")
         return
     for step, batch in enumerate(batches[:1 if steps == "one" else 2]):
-        _module_fwd_bwd(emb, ref, batch, perm_stream)
+        _module_fwd_bwd(emb, ref, batch, perm_stream, counted)
         apply()
+        assert len(counted.built) == step + 1  # none at apply
         ref.update(*batch)
         check(f"step {step}")
 
 
 @requires_gpu
 def test_module_pending_permutation_lifetime(monkeypatch):
-    """The pending permutation is matched to its ids by address, so it
-    must not outlive them: a forward without grad starts none and drops an
-    older one, and ``clear_pending`` drops it with the sinks."""
+    """A prefetched permutation lives on its forward's ``ctx`` and then in
+    its backward's record, nowhere else: a forward without grad starts
+    none and leaves no record, a grad-mode forward starts exactly one, and
+    after ``clear_pending`` nothing is left for an apply to launch or
+    build."""
     from tf_yarn_amd.models.sharded_embedding import \
         ShardedCriteoEmbeddings
     monkeypatch.setenv("MIYARN_BINNED_SCATTER", "1")
     emb = ShardedCriteoEmbeddings(MOD_TABLES, DIM).cuda()
-    ids = _module_batch("uniform", torch.Generator().manual_seed(16))[0]
+    ids, g_buf, g_wide = _module_batch("uniform",
+                                       torch.Generator().manual_seed(16))
+    counted = _CountedPermutation(monkeypatch)
 
     def forward():
         buf = torch.zeros(MOD_B, len(MOD_TABLES) * DIM, device="cuda")
         return emb(ids.cuda(), buf, 0)
 
-    forward()
-    assert emb._pending_perm is not None
     with torch.no_grad():
         forward()
-    assert emb._pending_perm is None
-    forward()
-    assert emb._pending_perm is not None
+    assert len(counted.built) == 0 and not emb.pending_grads()
+    out, wide = forward()
+    assert len(counted.built) == 1
+    torch.autograd.backward([out, wide],
+                            [g_buf.float().cuda(), g_wide.float().cuda()])
+    (record,) = emb.pending_grads()
+    assert record.perm[0] is counted.built[0]
     emb.clear_pending()
-    assert emb._pending_perm is None
+    assert emb.pending_grads() == []
+    launched = []
+    for name in ("emb_bwd_sgd_binned", "emb_scatter_sum_binned",
+                 "emb_bwd_sgd_fused_wide", "emb_bwd_sgd", "emb_scatter_sum"):
+        monkeypatch.setattr(ops, name,
+                            lambda *a, _n=name, **kw: launched.append(_n))
+    before = (emb.weight.detach().clone(), emb.wide_weight.detach().clone())
+    emb.apply_sparse_updates(LR)
     torch.cuda.synchronize()
+    assert not launched and len(counted.built) == 1
+    assert torch.equal(emb.weight.detach(), before[0])
+    assert torch.equal(emb.wide_weight.detach(), before[1])

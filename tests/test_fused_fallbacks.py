@@ -174,7 +174,8 @@ def _train_two_steps(monkeypatch, switch):
         opt.zero_grad(set_to_none=True)
         loss = model(dense, ids, labels=labels)
         loss.backward()
-        assert not model.embeddings._raw_ids_keys  # CPU keeps flat ids
+        (record,) = model.embeddings.pending_grads()
+        assert not record.raw_ids  # CPU keeps flat ids
         opt.step()
         model.apply_sparse_updates(lr=0.05)
         losses.append(loss.detach().clone())

@@ -253,7 +253,9 @@ def _train_two_steps(monkeypatch, switch):
         opt.zero_grad(set_to_none=True)
         loss = model(dense, ids, labels=labels)
         loss.backward()
-        raw_entries.append(len(model.embeddings._raw_ids_keys))
+        # exactly one pending record; 1 if it holds raw ids, else 0
+        (record,) = model.embeddings.pending_grads()
+        raw_entries.append(int(record.raw_ids))
         opt.step()
         model.apply_sparse_updates(lr=0.05)
         losses.append(loss.detach().clone())
@@ -274,3 +276,69 @@ def test_model_two_steps_switches_on_equal_off(monkeypatch):
     for (name, p), (_, q) in zip(on.named_parameters(),
                                  off.named_parameters()):
         assert torch.equal(p, q), name
+
+
+@requires_gpu
+def test_one_ids_tensor_two_forwards_one_apply(monkeypatch):
+    """The SAME ids tensor goes through two forwards before one apply, on
+    the raw-id path (atomic scatter, fused lookup, SGD, world 1).  Each
+    backward leaves its own record, so each deep gradient is applied with
+    its own wide gradient by the fused deep+wide kernel, from raw ids plus
+    offsets; no single-table kernel runs.  Integer operands and alpha =
+    -0.5 keep every sum exact in any order."""
+    from tf_yarn_amd.models.sharded_embedding import \
+        ShardedCriteoEmbeddings
+    monkeypatch.setenv("MIYARN_BINNED_SCATTER", "0")
+    monkeypatch.setenv("MIYARN_FUSED_LOOKUP", "1")
+    tables, dim, b, col = [50] * 4, 16, 200, 16
+    f, rows = len(tables), sum(tables)
+    # worst case: every example of both backwards hits one row
+    assert 2 * AMAX * b * LR + AMAX < exact_ints.EXACT_LIMIT
+    gen = torch.Generator().manual_seed(21)
+    deep = exact_ints.ints((rows, dim), AMAX, gen)
+    wide = exact_ints.ints((rows, 1), AMAX, gen)
+    emb = ShardedCriteoEmbeddings(tables, dim).cuda()
+    assert emb.world == 1
+    with torch.no_grad():
+        emb.weight.copy_(deep.float())
+        emb.wide_weight.copy_(wide.float())
+    ids = torch.randint(0, tables[0], (b, f), generator=gen)
+    dense = torch.randn(b, 13, generator=gen).cuda()
+    ids_gpu = ids.cuda()
+    assert ids_gpu.is_contiguous()
+
+    calls = {"emb_bwd_sgd_fused_wide": [], "emb_bwd_sgd": [],
+             "emb_scatter_sum": []}
+    for name, log in calls.items():
+        def counted(*a, _fn=getattr(ops, name), _log=log, **kw):
+            _log.append(kw.get("offsets"))
+            return _fn(*a, **kw)
+        monkeypatch.setattr(ops, name, counted)
+
+    flat = (ids + _offsets(f, tables[0], False)).reshape(-1)
+    want_deep, want_wide = deep.double(), wide.double()
+    for _ in range(2):
+        buf = torch.empty(b, col + f * dim, device="cuda")
+        out, wide_sum = emb(ids_gpu, buf, col, dense=dense)
+        g_buf = exact_ints.ints((b, col + f * dim), AMAX, gen)
+        g_wide = exact_ints.ints((b,), AMAX, gen)
+        torch.autograd.backward([out, wide_sum],
+                                [g_buf.float().cuda(), g_wide.float().cuda()])
+        want_deep.index_add_(0, flat,
+                             g_buf[:, col:].double().reshape(-1, dim),
+                             alpha=-LR)
+        want_wide.index_add_(
+            0, flat, g_wide.double().repeat_interleave(f).reshape(-1, 1),
+            alpha=-LR)
+    records = emb.pending_grads()
+    assert len(records) == 2 and all(r.raw_ids for r in records)
+    assert not any(calls.values())
+    emb.apply_sparse_updates(LR)
+    torch.cuda.synchronize()
+    assert not emb.pending_grads()
+    assert len(calls["emb_bwd_sgd_fused_wide"]) == 2
+    assert all(o is emb.full_offsets
+               for o in calls["emb_bwd_sgd_fused_wide"])
+    assert not calls["emb_bwd_sgd"] and not calls["emb_scatter_sum"]
+    assert torch.equal(emb.weight.detach().cpu(), want_deep.float())
+    assert torch.equal(emb.wide_weight.detach().cpu(), want_wide.float())

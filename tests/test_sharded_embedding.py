@@ -7,6 +7,7 @@ import torch
 import torch.multiprocessing as mp
 from torch import nn
 
+import exact_ints
 from tf_yarn_amd.kv import KVClient, KVServer
 
 F, D, ROWS, B, W = 4, 8, 50, 6, 2
@@ -192,3 +193,102 @@ def test_sharded_forward_world4_uneven_features():
                 p.terminate()
         server.stop()
     assert all(results.values()), results
+
+
+# ---- one record per backward (world 1) -------------------------------------
+
+def _int_tables(emb, gen):
+    """Integer-valued tables in ``emb``; their float64 copies."""
+    deep = exact_ints.ints((ROWS * F, D), 4, gen)
+    wide = exact_ints.ints((ROWS * F, 1), 4, gen)
+    emb.weight.data.copy_(deep.float())
+    emb.wide_weight.data.copy_(wide.float())
+    return deep.double(), wide.double()
+
+
+@pytest.mark.parametrize("order", ["a_then_b", "b_then_a"])
+def test_two_forwards_at_different_col_offsets(order):
+    """Forward A fills a buffer from column 0, forward B one from column 16
+    behind the dense columns; each backward must slice ITS buffer's
+    gradient at its own forward's ``col_offset``, whichever runs first.
+    Integer operands and lr 0.5: the float64 ``index_add_`` of both tables
+    comes back exactly."""
+    from tf_yarn_amd.models.sharded_embedding import \
+        ShardedCriteoEmbeddings
+    b, lr, pad = 32, 0.5, 16
+    gen = torch.Generator().manual_seed(31)
+    emb = ShardedCriteoEmbeddings(TABLES, D)
+    assert emb.world == 1
+    want_deep, want_wide = _int_tables(emb, gen)
+    assert 2 * 4 * b * lr + 4 < exact_ints.EXACT_LIMIT
+    offs = torch.arange(F) * ROWS
+    runs = {}
+    for name, col in (("a", 0), ("b", pad)):
+        ids = torch.randint(0, ROWS, (b, F), generator=gen)
+        buf = torch.zeros(b, col + F * D)
+        dense = torch.randn(b, 13, generator=gen) if col else None
+        out, wide_out = emb(ids, buf, col, dense=dense)
+        g_buf = exact_ints.ints((b, col + F * D), 4, gen)
+        g_wide = exact_ints.ints((b,), 4, gen)
+        runs[name] = (out, wide_out, g_buf.float(), g_wide.float())
+        flat = (ids + offs).reshape(-1)
+        want_deep.index_add_(0, flat,
+                             g_buf[:, col:].double().reshape(-1, D),
+                             alpha=-lr)
+        want_wide.index_add_(
+            0, flat, g_wide.double().repeat_interleave(F).reshape(-1, 1),
+            alpha=-lr)
+    for name in (("a", "b") if order == "a_then_b" else ("b", "a")):
+        out, wide_out, g_buf, g_wide = runs[name]
+        torch.autograd.backward([out, wide_out], [g_buf, g_wide])
+    assert len(emb.pending_grads()) == 2
+    emb.apply_sparse_updates(lr)
+    assert not emb.pending_grads()
+    assert torch.equal(emb.weight.detach(), want_deep.float())
+    assert torch.equal(emb.wide_weight.detach(), want_wide.float())
+
+
+@pytest.mark.parametrize("deep_rule,wide_rule",
+                         [("adagrad", "adagrad"), ("adagrad", "ftrl"),
+                          ("lazy_adam", "lazy_adam")])
+def test_each_record_applies_its_own_pair(deep_rule, wide_rule, monkeypatch):
+    """Two forwards and backwards, one apply, two stateful tables: every
+    record goes to ``ops.emb_bwd_sparse`` once, as a pair whose two sides
+    carry the gradients of that record, in the records' order."""
+    from tf_yarn_amd import ops
+    from tf_yarn_amd.models.sharded_embedding import \
+        ShardedCriteoEmbeddings
+    b = 32
+    gen = torch.Generator().manual_seed(32)
+    torch.manual_seed(33)
+    emb = ShardedCriteoEmbeddings(TABLES, D, sparse_optimizer=deep_rule,
+                                  wide_sparse_optimizer=wide_rule)
+    for _ in range(2):
+        ids = torch.randint(0, ROWS, (b, F), generator=gen)
+        out, wide_out = emb(ids, torch.zeros(b, F * D), 0)
+        torch.autograd.backward(
+            [out, wide_out], [torch.randn(b, F * D, generator=gen),
+                              torch.randn(b, generator=gen)])
+    want = [(r.ids, r.deep_grad.clone(), r.wide_grad.clone())
+            for r in emb.pending_grads()]
+    assert len(want) == 2
+    assert not torch.equal(want[0][1], want[1][1])
+    assert not torch.equal(want[0][2], want[1][2])
+    calls = []
+    real = ops.emb_bwd_sparse
+
+    def recorder(ids, *, deep=None, wide=None, **kw):
+        calls.append((ids, deep, wide))
+        return real(ids, deep=deep, wide=wide, **kw)
+
+    monkeypatch.setattr(ops, "emb_bwd_sparse", recorder)
+    emb.apply_sparse_updates(LR)
+    assert len(calls) == 2
+    for (ids, deep, wide), (w_ids, w_deep, w_wide) in zip(calls, want):
+        assert ids is w_ids
+        assert (deep.rule, wide.rule) == (deep_rule, wide_rule)
+        assert torch.equal(deep.grad.reshape(b, F * D), w_deep)
+        assert torch.equal(wide.grad, w_wide)
+    if deep_rule == "lazy_adam":
+        assert emb.adam_step_count("") == 2
+        assert emb.adam_step_count("wide_") == 2

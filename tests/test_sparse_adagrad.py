@@ -9,6 +9,7 @@ import torch
 import torch.multiprocessing as mp
 from torch import nn
 
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.kv import KVClient, KVServer
 from tf_yarn_amd.models.wide_deep import (FlatInputWideAndDeep,
@@ -127,19 +128,12 @@ def _tables(model):
     return d.weight, d.state_sum, w.weight, w.state_sum
 
 
-def _sinks(model):
-    if model.sharded:
-        return model.embeddings._deep_sink, model.embeddings._wide_sink
-    return (model.deep_embedding.pending_grads(),
-            model.wide_embedding.pending_grads())
-
-
 def _step_and_check(model, seed):
     """backward, read the sinks, apply through the model and through the
     reference op on copies; both must agree."""
     dense, ids, labels = _batch(seed)
     model(dense, ids, labels=labels).backward()
-    deep_sink, wide_sink = _sinks(model)
+    deep_sink, wide_sink = sink_pairs(model)
     (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in deep_sink]
     (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in wide_sink]
     dt, ds, wt, ws = [t.detach().clone() for t in _tables(model)]
@@ -149,7 +143,7 @@ def _step_and_check(model, seed):
     ops.emb_bwd_adagrad_wide(wt, ws, w_ids, w_grad, lr=LR)
     for got, want in zip(_tables(model), (dt, ds, wt, ws)):
         assert torch.allclose(got.detach(), want, atol=1e-6)
-    assert not deep_sink and not wide_sink
+    assert sink_pairs(model) == ([], [])
 
 
 @pytest.mark.parametrize("sharded", [False, True])

@@ -25,6 +25,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.kv import KVClient, KVServer
 from tf_yarn_amd.models.wide_deep import (SPARSE_OPTIMIZERS,
@@ -333,17 +334,16 @@ def test_recipe_model_applies_the_reference_ops(sharded):
         e = model.embeddings
         got = (e.weight, e.state_sum, e.wide_weight, e.wide_ftrl_accum,
                e.wide_ftrl_linear)
-        sinks = (e._deep_sink, e._wide_sink)
     else:
         d, w = model.deep_embedding, model.wide_embedding
         got = (d.weight, d.state_sum, w.weight, w.ftrl_accum,
                w.ftrl_linear)
-        sinks = (d.pending_grads(), w.pending_grads())
     for seed in (10, 11):
         dense, ids, labels = _batch(seed)
         model(dense, ids, labels=labels).backward()
-        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in wide_sink]
         dt, ds, wt, wn, wz = [t.detach().clone() for t in got]
         model.apply_sparse_updates(LR)
         ops.emb_bwd_adagrad(dt, ds, d_ids,
@@ -353,7 +353,7 @@ def test_recipe_model_applies_the_reference_ops(sharded):
                               l1=L1, l2=L2)
         for a, b in zip(got, (dt, ds, wt, wn, wz)):
             assert torch.allclose(a.detach(), b, atol=1e-6)
-        assert not sinks[0] and not sinks[1]
+        assert sink_pairs(model) == ([], [])
     assert got[4].abs().sum() > 0
     # different knobs give a different table
     other = torch.zeros_like(wt)

@@ -21,6 +21,7 @@ import collections
 import pytest
 import torch
 
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.models.synthetic import synthetic_criteo_batch
 from tf_yarn_amd.models.wide_deep import WideAndDeep
@@ -232,18 +233,17 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
         e = model.embeddings
         params = (e.weight, e.state_sum, e.wide_weight, e.wide_ftrl_accum,
                   e.wide_ftrl_linear)
-        sinks = (e._deep_sink, e._wide_sink)
     else:
         d, w = model.deep_embedding, model.wide_embedding
         params = (d.weight, d.state_sum, w.weight, w.ftrl_accum,
                   w.ftrl_linear)
-        sinks = (d.pending_grads(), w.pending_grads())
     for step in range(2):
         dense, ids, labels = synthetic_criteo_batch(
             256, tables, device="cuda", seed=step)
         model(dense, ids % 12, labels=labels).backward()
-        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in wide_sink]
         dt, ds, wt, wn, wz = [p.detach().cpu().clone() for p in params]
         model.apply_sparse_updates(LR)
         ops.emb_bwd_adagrad(dt, ds, d_ids,

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from lazy_adam_refs import exact_grads, lazy_adam_step64, wide_rows
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.models.wide_deep import (ADAM_SPARSE_OPTIMIZERS,
                                           DEEP_SPARSE_OPTIMIZERS,
@@ -376,17 +377,16 @@ def test_model_applies_the_reference_op_with_its_scalars(sharded):
         e = model.embeddings
         got = (e.weight, e.adam_exp_avg, e.adam_exp_avg_sq, e.wide_weight,
                e.wide_adam_exp_avg, e.wide_adam_exp_avg_sq)
-        sinks = (e._deep_sink, e._wide_sink)
     else:
         d, w = model.deep_embedding, model.wide_embedding
         got = (d.weight, d.adam_exp_avg, d.adam_exp_avg_sq, w.weight,
                w.adam_exp_avg, w.adam_exp_avg_sq)
-        sinks = (d.pending_grads(), w.pending_grads())
     for step, seed in enumerate((10, 11, 12), start=1):
         dense, ids, labels = _batch(seed)
         model(dense, ids, labels=labels).backward()
-        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in wide_sink]
         want = [t.detach().clone() for t in got]
         model.apply_sparse_updates(LR)
         ops.emb_bwd_lazy_adam(*want[:3], d_ids,
@@ -396,7 +396,7 @@ def test_model_applies_the_reference_op_with_its_scalars(sharded):
                                    **dict(KW, lr=0.3))
         for a, b in zip(got, want):
             assert torch.equal(a.detach(), b), step
-        assert not sinks[0] and not sinks[1]
+        assert sink_pairs(model) == ([], [])
 
 
 @pytest.mark.parametrize("sharded", [False, True])

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from test_sparse_ftrl_gpu import _all_close, _close, _exact_grads
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.models.synthetic import synthetic_criteo_batch
 from tf_yarn_amd.models.wide_deep import WideAndDeep
@@ -372,18 +373,17 @@ def test_model_update_runs_the_hip_kernels(sharded, monkeypatch):
         e = model.embeddings
         params = (e.weight, e.adam_exp_avg, e.adam_exp_avg_sq,
                   e.wide_weight, e.wide_adam_exp_avg, e.wide_adam_exp_avg_sq)
-        sinks = (e._deep_sink, e._wide_sink)
     else:
         d, w = model.deep_embedding, model.wide_embedding
         params = (d.weight, d.adam_exp_avg, d.adam_exp_avg_sq, w.weight,
                   w.adam_exp_avg, w.adam_exp_avg_sq)
-        sinks = (d.pending_grads(), w.pending_grads())
     for step in (1, 2, 3):
         dense, ids, labels = synthetic_criteo_batch(
             256, tables, device="cuda", seed=step)
         model(dense, ids % 12, labels=labels).backward()
-        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in wide_sink]
         want = [p.detach().cpu().clone() for p in params]
         model.apply_sparse_updates(LR)
         ops.emb_bwd_lazy_adam(*want[:3], d_ids,

@@ -20,6 +20,7 @@ import pickle
 import pytest
 import torch
 
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.models import wide_deep
 from tf_yarn_amd.models.wide_deep import (SPARSE_OPTIMIZERS,
@@ -232,20 +233,19 @@ def test_model_applies_the_reference_ops(sharded, wide_rule):
         e = model.embeddings
         deep_got = (e.weight, e.state_sum_row)
         wide_w, wp, wide_owner = e.wide_weight, "wide_", e
-        sinks = (e._deep_sink, e._wide_sink)
     else:
         d, w = model.deep_embedding, model.wide_embedding
         deep_got = (d.weight, d.state_sum_row)
         wide_w, wp, wide_owner = w.weight, "", w
-        sinks = (d.pending_grads(), w.pending_grads())
     wide_names = {"adagrad": ["state_sum"], "sgd": [],
                   "ftrl": ["ftrl_accum", "ftrl_linear"]}[wide_rule]
     wide_got = [wide_w] + [getattr(wide_owner, wp + n) for n in wide_names]
     for seed in (10, 11):
         dense, ids, labels = _batch(seed)
         model(dense, ids, labels=labels).backward()
-        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.clone(), g.clone()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.clone(), g.clone()) for i, g in wide_sink]
         dt, ds = [t.detach().clone() for t in deep_got]
         wt = [t.detach().clone() for t in wide_got]
         model.apply_sparse_updates(LR)
@@ -262,7 +262,7 @@ def test_model_applies_the_reference_ops(sharded, wide_rule):
                                 alpha=-wide_lr)
         for a, b in zip(list(deep_got) + wide_got, [dt, ds] + wt):
             assert torch.allclose(a.detach(), b, atol=1e-6)
-        assert not sinks[0] and not sinks[1]
+        assert sink_pairs(model) == ([], [])
     assert (deep_got[1] != INIT).any() and (deep_got[1] == INIT).any()
 
 

@@ -17,6 +17,7 @@ import collections
 import pytest
 import torch
 
+from sink_pairs import sink_pairs
 from tf_yarn_amd import ops
 from tf_yarn_amd.models.synthetic import synthetic_criteo_batch
 from tf_yarn_amd.models.wide_deep import WideAndDeep
@@ -283,21 +284,20 @@ def test_model_update_runs_the_hip_kernels(sharded, wide_rule, monkeypatch):
         e = model.embeddings
         params = [e.weight, e.state_sum_row, e.wide_weight] + \
             [getattr(e, "wide_" + n) for n in wide_names]
-        sinks = (e._deep_sink, e._wide_sink)
         assert not hasattr(e, "state_sum")
     else:
         d, w = model.deep_embedding, model.wide_embedding
         params = [d.weight, d.state_sum_row, w.weight] + \
             [getattr(w, n) for n in wide_names]
-        sinks = (d.pending_grads(), w.pending_grads())
         assert not hasattr(d, "state_sum")
     assert params[1].shape == (sum(tables),)
     for step in range(2):
         dense, ids, labels = synthetic_criteo_batch(
             256, tables, device="cuda", seed=step)
         model(dense, ids % 12, labels=labels).backward()
-        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[0]]
-        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in sinks[1]]
+        deep_sink, wide_sink = sink_pairs(model)
+        (d_ids, d_grad), = [(i.cpu(), g.float().cpu()) for i, g in deep_sink]
+        (w_ids, w_grad), = [(i.cpu(), g.float().cpu()) for i, g in wide_sink]
         want = [p.detach().cpu().clone() for p in params]
         model.apply_sparse_updates(LR)
         ops.emb_bwd_rowwise_adagrad(

@@ -187,3 +187,16 @@ def test_estimator_train_applies_sparse_updates(tmp_path):
     assert not torch.equal(net.deep_embedding.weight, before), \
         "embedding table did not train through Estimator.train"
     assert not net.deep_embedding.pending_grads(), "sink leaked"
+
+
+def test_replicated_modules_share_one_sparse_sync():
+    """The deep and the wide replicated table run ONE implementation of
+    the data-parallel sync; what differs between them are two hooks."""
+    from tf_yarn_amd.models.wide_deep import WideScalarEmbedding
+    for name in ("start_sparse_sync", "finish_sparse_sync",
+                 "apply_sparse_updates", "clear_pending", "pending_grads"):
+        assert getattr(SparseEmbedding, name) is \
+            getattr(WideScalarEmbedding, name), name
+    for hook in ("_update_rows", "_sgd_update"):
+        assert getattr(SparseEmbedding, hook) is not \
+            getattr(WideScalarEmbedding, hook), hook

@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import logging
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -37,7 +37,8 @@ from torch import nn
 
 from tf_yarn_amd import ops
 from tf_yarn_amd.models.wide_deep import (SparseOptimizerMixin,
-                                          _default_wide_rule)
+                                          _default_wide_rule,
+                                          _table_offsets)
 from tf_yarn_amd.utils import commprobe
 
 logger = logging.getLogger(__name__)
@@ -174,9 +175,24 @@ def _all_to_all_single(output: torch.Tensor, input_: torch.Tensor,
         offset += n
 
 
+class ShardedUpdate(NamedTuple):
+    """What one ``_ShardedLookup.backward`` leaves for the apply: the
+    owner-local ids with the deep and the wide gradient that belong to
+    them."""
+    ids: torch.Tensor
+    deep_grad: torch.Tensor
+    wide_grad: torch.Tensor
+    # ids is the raw [B, F] array of the W == 1 fused lookup: full_offsets
+    # is still to be added (the fused SGD scatter adds it in the kernel)
+    raw_ids: bool
+    # ((order, starts), event or None): the binned permutation of ``ids``
+    # that forward prefetched, or None
+    perm: Optional[tuple]
+
+
 class _ShardedLookup(torch.autograd.Function):
     """Forward/backward all-to-all routing around the owner-local fused
-    gather; backward stashes owner-local (ids, grads) in the sink."""
+    gather; backward leaves one :class:`ShardedUpdate` with the module."""
 
     @staticmethod
     def forward(ctx, deep_table, wide_table, module, ids, deep_out_buf,
@@ -188,7 +204,10 @@ class _ShardedLookup(torch.autograd.Function):
         W, B = m.world, ids.shape[0]
         D = m.dim
         device = ids.device
+        ctx.module = m
+        ctx.col_offset = col_offset
         ctx.raw_ids = False
+        ctx.perm = None  # dropped with the ctx if no backward follows
 
         if W == 1 and dense is not None and m._fused_lookup_ok(
                 ids, dense, deep_out_buf, col_offset):
@@ -207,8 +226,7 @@ class _ShardedLookup(torch.autograd.Function):
                 ctx.raw_ids = True
             else:
                 saved = (ids + m.full_offsets.unsqueeze(0)).reshape(-1)
-                m._start_perm_async(saved, grad_enabled)
-            ctx.module = m
+                ctx.perm = m._start_perm_async(saved, grad_enabled)
             ctx.save_for_backward(saved)
             ctx.local_only = True
             ctx.mark_dirty(deep_out_buf)
@@ -223,8 +241,7 @@ class _ShardedLookup(torch.autograd.Function):
             ops.emb_fwd_into(deep_table, flat, deep_out_buf, col_offset)
             wide_out = ops.emb_gather_sum(wide_table, flat.reshape(B, -1),
                                           m.out_bf16)
-            m._start_perm_async(flat, grad_enabled)
-            ctx.module = m
+            ctx.perm = m._start_perm_async(flat, grad_enabled)
             ctx.save_for_backward(flat)
             ctx.local_only = True
             ctx.mark_dirty(deep_out_buf)
@@ -243,7 +260,7 @@ class _ShardedLookup(torch.autograd.Function):
         # local row offsets: layout [peer][b][j], j = feature slot
         flat_local = ids_recv + m.own_offsets_tiled[:ids_recv.numel()]
 
-        m._start_perm_async(flat_local, grad_enabled)
+        ctx.perm = m._start_perm_async(flat_local, grad_enabled)
 
         # ---- owner-local gathers ----------------------------------------
         vec = ops.emb_fwd(deep_table, flat_local, m.out_bf16)  # [W*n_own, D]
@@ -276,7 +293,6 @@ class _ShardedLookup(torch.autograd.Function):
                                [B] * W, [B] * W, m.group)
         wide_out = wide_recv.reshape(W, B).sum(dim=0)
 
-        ctx.module = m
         ctx.save_for_backward(flat_local)
         ctx.local_only = False
         ctx.B = B
@@ -289,9 +305,8 @@ class _ShardedLookup(torch.autograd.Function):
         (flat_ids,) = ctx.saved_tensors
         W, D = m.world, m.dim
         # grad_deep_buf is the WHOLE MLP-input grad; the embedding slice
-        # starts at the col_offset recorded by the module
-        col_offset = m._last_col_offset
-        emb_grad = grad_deep_buf[:, col_offset:]
+        # starts at this forward's col_offset
+        emb_grad = grad_deep_buf[:, ctx.col_offset:]
         if ctx.local_only:
             # The fused deep+wide SGD kernel reads the column slice where
             # it lies (no 54 MB gather copy per step at the bench shape);
@@ -300,10 +315,9 @@ class _ShardedLookup(torch.autograd.Function):
                     and emb_grad.stride(1) == 1 and not m._stateful()
                     and emb_grad.dtype == grad_wide.dtype):
                 emb_grad = emb_grad.contiguous()
-            if ctx.raw_ids:  # [B, F] raw ids: the apply adds the offsets
-                m._raw_ids_keys.add(flat_ids.data_ptr())
-            m._deep_sink.append((flat_ids, emb_grad))
-            m._wide_sink.append((flat_ids, grad_wide.contiguous()))
+            m._pending.append(ShardedUpdate(
+                flat_ids, emb_grad, grad_wide.contiguous(), ctx.raw_ids,
+                ctx.perm))
             return None, None, None, None, None, None, None, None
         B = ctx.B
         n_own = B * m.f_own
@@ -323,13 +337,13 @@ class _ShardedLookup(torch.autograd.Function):
             _all_to_all_single(
                 g_recv, g_send, [n_own * D] * W,
                 [B * len(m.feats_of[s]) * D for s in range(W)], m.group)
-        m._deep_sink.append((flat_ids, g_recv.reshape(W * n_own, D)))
         # wide: every owner needs every rank's grad_wide [B]
         gw = grad_wide.contiguous().reshape(-1)
         gw_all = torch.empty(W * B, dtype=gw.dtype, device=gw.device)
         with commprobe.span("ag_wide"):
             dist.all_gather_into_tensor(gw_all, gw, group=m.group)
-        m._wide_sink.append((flat_ids, gw_all))
+        m._pending.append(ShardedUpdate(
+            flat_ids, g_recv.reshape(W * n_own, D), gw_all, False, ctx.perm))
         return None, None, None, None, None, None, None, None
 
 
@@ -398,31 +412,21 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
              "wide_": (self.wide_weight, wide_sparse_optimizer)},
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
             wide_sparse_lr=wide_sparse_lr, sparse_betas=sparse_betas)
-        offs = torch.tensor(
-            [0] + list(torch.cumsum(torch.tensor(own_sizes), 0)[:-1]),
-            dtype=torch.int64)
+        offs = _table_offsets(own_sizes)
         # PER-RANK buffers (different size/content on each rank): they must
         # never be broadcast by the reducer — flagged _miyarn_sharded,
         # which BucketedDataParallel skips.
         offs._miyarn_sharded = True
         self.register_buffer("own_offsets", offs, persistent=True)
         # full offsets for the W == 1 local path (perm == identity there)
-        full = torch.tensor(
-            [0] + list(torch.cumsum(torch.tensor(table_sizes), 0)[:-1]),
-            dtype=torch.int64)
-        self.register_buffer("full_offsets", full, persistent=True)
+        self.register_buffer("full_offsets", _table_offsets(table_sizes),
+                             persistent=True)
         tiled0 = torch.empty(0, dtype=torch.int64)
         tiled0._miyarn_sharded = True
         self.register_buffer("own_offsets_tiled", tiled0,
                              persistent=False)
-        self._deep_sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
-        self._wide_sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
-        self._last_col_offset = 0
-        # data_ptr of sink entries that hold RAW [B, F] ids (W == 1 fused
-        # lookup): the fused scatter adds full_offsets in the kernel
-        self._raw_ids_keys: set = set()
+        self._pending: List[ShardedUpdate] = []  # one per backward
         self._perm_stream = None  # side stream for async pass A
-        self._pending_perm = None  # (ids data_ptr, (order, starts), event)
         self._binned_auto: Optional[bool] = None  # skew probe result
 
     def _ensure_tiled(self, numel: int, device) -> None:
@@ -441,7 +445,6 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         col_offset``, in the buffer's dtype) the columns in front of the
         slice are written here too: ``dense``, then zeros up to
         ``col_offset``; without it they are the caller's."""
-        self._last_col_offset = col_offset
         if self.world > 1:
             self._ensure_tiled(self.world * ids.shape[0] * self.f_own,
                                ids.device)
@@ -493,49 +496,51 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         if stream is not None:
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):
-                for flat_ids, grad in self._deep_sink:
-                    flat_ids.record_stream(stream)
-                    grad.record_stream(stream)
-                for flat_ids, gw in self._wide_sink:
-                    flat_ids.record_stream(stream)
-                    gw.record_stream(stream)
+                for rec in self._pending:
+                    for t in (rec.ids, rec.deep_grad, rec.wide_grad):
+                        t.record_stream(stream)
                 self._apply_pending(lr)
             return
         self._apply_pending(lr)
 
+    def pending_grads(self) -> List[ShardedUpdate]:
+        """The records of the backwards since the last apply, oldest
+        first."""
+        return self._pending
+
+    def _binned_permutation(self, flat_ids: torch.Tensor):
+        rows = self.weight.shape[0]
+        return ops.binned_permutation(
+            flat_ids, rows, ops.pick_region_bits(rows, flat_ids.numel()))
+
     def _start_perm_async(self, flat_ids: torch.Tensor,
-                          grad_enabled: bool) -> None:
+                          grad_enabled: bool) -> Optional[tuple]:
         """Kick off the binned-scatter permutation (pass A) on a side
         stream DURING FORWARD: it depends only on the ids, and its
         ~200 us of latency/atomic-bound work hides under the MFMA-bound
         MLP GEMMs instead of sitting on the backward critical path.
         ``grad_enabled`` is the grad mode of the module's forward call
         (inside ``_ShardedLookup.forward`` autograd has switched it off):
-        only a forward that a backward can follow starts one.  An older
-        permutation that was never applied is dropped."""
-        self._pending_perm = None
+        only a forward that a backward can follow starts one.  Returns
+        ``(permutation, event)`` (event None: built inline) for the
+        forward's ``ctx``, or None."""
         if self._stateful():
-            return  # the binned scatter is an SGD kernel
+            return None  # the binned scatter is an SGD kernel
         if not (flat_ids.is_cuda and self.dim == 16 and ops.HAVE_EXT
                 and grad_enabled and self._binned_on(flat_ids)):
-            return
-        rb = ops.pick_region_bits(self.weight.shape[0], flat_ids.numel())
+            return None
         if not _perm_stream_enabled():
             # inline (A/B diagnostic): pass A runs on the main stream
-            perm = ops.binned_permutation(flat_ids, self.weight.shape[0],
-                                          rb)
-            self._pending_perm = (flat_ids.data_ptr(), perm, None)
-            return
+            return self._binned_permutation(flat_ids), None
         if self._perm_stream is None:
             self._perm_stream = torch.cuda.Stream()
         self._perm_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._perm_stream):
             flat_ids.record_stream(self._perm_stream)
-            perm = ops.binned_permutation(flat_ids, self.weight.shape[0],
-                                          rb)
+            perm = self._binned_permutation(flat_ids)
         ev = torch.cuda.Event()
         ev.record(self._perm_stream)
-        self._pending_perm = (flat_ids.data_ptr(), perm, ev)
+        return perm, ev
 
     def _binned_on(self, flat_ids: torch.Tensor) -> bool:
         """Resolve the binned-vs-atomic choice (see ``_binned_mode``)."""
@@ -561,160 +566,108 @@ class ShardedCriteoEmbeddings(SparseOptimizerMixin, nn.Module):
         return (self.sparse_optimizer, self.wide_sparse_optimizer) != \
             ("sgd", "sgd")
 
-    def _apply_pending_stateful(self, lr: float) -> None:
-        """Owner-local update when at least one table has a stateful rule
-        (Adagrad, FTRL, lazy Adam, row-wise Adagrad).  Deep and wide sink
-        entries that share their flat ids go to ``ops.emb_bwd_sparse`` as one pair when
-        both rules are stateful: it runs the pair's fused deep+wide kernel
-        where there is one (ids read once per pass, one claim per row for
-        both tables) and the two single-table updates otherwise.  An SGD
-        side is applied here, next to a single-table stateful call.  The
-        binned scatter is never used here."""
-        scale = 1.0 / self.world
-        deep_rule, wide_rule = (self.sparse_optimizer,
-                                self.wide_sparse_optimizer)
-        wide_lr = lr if self.wide_sparse_lr is None else self.wide_sparse_lr
-        deep, wide = self.weight.data, self.wide_weight.data
-        if deep_rule == "sgd":
-            deep_ws, wide_ws = None, self._adagrad_workspace(wide)
-        elif wide_rule == "sgd":
-            deep_ws, wide_ws = self._adagrad_workspace(deep), None
-        else:
-            deep_ws = self._adagrad_workspace(deep, wide)
-            wide_ws = deep_ws.wide_view()
-        both_stateful = "sgd" not in (deep_rule, wide_rule)
-        wide_by_ids = {gw_ids.data_ptr(): (i, gw)
-                       for i, (gw_ids, gw) in enumerate(self._wide_sink)}
-        paired_wide_done = set()
-        for flat_ids, grad in self._deep_sink:
-            grad2d = grad.reshape(flat_ids.numel(), self.dim)
-            mate = wide_by_ids.get(flat_ids.data_ptr())
-            if (both_stateful and mate is not None
-                    and mate[0] not in paired_wide_done):
-                ops.emb_bwd_sparse(
-                    flat_ids,
-                    deep=self._sparse_side(deep_rule, "", deep, grad2d, lr),
-                    wide=self._sparse_side(wide_rule, "wide_", wide,
-                                           mate[1], wide_lr),
-                    scale=scale, workspace=deep_ws)
-                paired_wide_done.add(mate[0])
-            elif deep_rule == "sgd":
-                ops.emb_bwd_sgd(deep, flat_ids, grad2d, lr=lr, scale=scale)
-            else:
-                self._sparse_apply_one(deep_rule, "", deep, flat_ids,
-                                       grad2d, lr, scale, deep_ws,
-                                       wide=False)
-        self._deep_sink.clear()
-        for i, (flat_ids, gw) in enumerate(self._wide_sink):
-            if i in paired_wide_done:
-                continue
-            if wide_rule == "sgd":
-                fan = self.F if self.world == 1 else self.f_own
-                ops.emb_scatter_sum(wide, flat_ids.reshape(gw.numel(), fan),
-                                    gw, alpha=-wide_lr * scale)
-            else:
-                self._sparse_apply_one(wide_rule, "wide_", wide, flat_ids,
-                                       gw, wide_lr, scale, wide_ws,
-                                       wide=True)
-        self._wide_sink.clear()
+    def _record_perm(self, rec: ShardedUpdate, flat_ids: torch.Tensor):
+        """The binned permutation of a record's ids: the one its forward
+        prefetched, or one built here."""
+        if rec.perm is None:
+            return self._binned_permutation(flat_ids)
+        perm, ev = rec.perm
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+        # built on the side stream or (inline) on the forward's, used on
+        # this one, which may be the caller's ``stream=``: keep the
+        # allocator from handing the blocks out while pass B reads them
+        for t in perm:
+            t.record_stream(torch.cuda.current_stream())
+        return perm
 
     def _apply_pending(self, lr: float) -> None:
-        if self._stateful():
-            self._apply_pending_stateful(lr)
-            return
+        """Owner-local update of both tables from the pending records,
+        oldest first.  Each record takes the first route that fits:
+
+        1. the pair as one call: ``ops.emb_bwd_sgd_fused_wide`` for two
+           SGD tables on the atomic path (one kernel reads the ids once
+           and issues both scatters; it adds ``full_offsets`` to raw ids
+           itself), ``ops.emb_bwd_sparse(deep=, wide=)`` for two stateful
+           tables (the pair's fused kernel where there is one, the two
+           single-table updates otherwise);
+        2. the deep side alone, then the wide side alone: the binned
+           scatters (two SGD tables only; one region-binned permutation
+           per record, shared by both, LDS dedup + exclusive-owner
+           writeback instead of random global atomics), an SGD side, or a
+           single-table stateful call.  A mixed SGD/stateful pair always
+           runs this way.
+
+        With more than one record the launches go D1 W1 D2 W2, not all
+        deep updates first: per table the order is the records', and the
+        two tables are different tensors, so every result keeps its bits.
+        MIYARN_BINNED_SCATTER=0 restores the atomic kernels for A/B
+        runs."""
+        records = self._pending
         scale = 1.0 / self.world
         wide_lr = lr if self.wide_sparse_lr is None else self.wide_sparse_lr
-        # Binned scatter (round-2 kernel): one region-binned permutation
-        # shared by the deep and wide updates (identical flat ids), LDS
-        # dedup + exclusive-owner writeback instead of 27M random global
-        # atomics.  MIYARN_BINNED_SCATTER=0 restores the atomic kernels
-        # for A/B runs.
-        first_ids = self._deep_sink[0][0] if self._deep_sink else None
-        use_binned = (self.weight.is_cuda and self.dim == 16
-                      and ops.HAVE_EXT and first_ids is not None
-                      and self._binned_on(first_ids))
-        perms = {}
-        if use_binned and self._pending_perm is not None:
-            key, perm, ev = self._pending_perm
-            if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
-            # built on the side stream or (inline) on the forward's, used
-            # on this one, which may be the caller's ``stream=``: keep the
-            # allocator from handing the blocks out while pass B reads them
-            for t in perm:
-                t.record_stream(torch.cuda.current_stream())
-            perms[key] = perm
-            self._pending_perm = None
-
-        def perm_for(flat_ids):
-            key = flat_ids.data_ptr()
-            if key not in perms:
-                rb = ops.pick_region_bits(self.weight.shape[0],
-                                          flat_ids.numel())
-                perms[key] = ops.binned_permutation(
-                    flat_ids, self.weight.shape[0], rb)
-            return perms[key]
-
-        # Atomic fast path: deep+wide updates share the same flat ids, so
-        # one fused kernel reads the ids once and issues both scatters
-        # (saves the wide kernel's launch + its 13.6 MB id re-read).
-        wide_by_ids = {gw_ids.data_ptr(): (i, gw)
-                       for i, (gw_ids, gw) in enumerate(self._wide_sink)}
-        fused_wide_done = set()
-        raw_keys = self._raw_ids_keys
-
-        def flat_of(ids):
-            # raw [B, F] ids that did not get the fused kernel after all
-            if ids.data_ptr() in raw_keys and ids.dim() == 2:
-                return (ids + self.full_offsets.unsqueeze(0)).reshape(-1)
-            return ids
-
-        for flat_ids, grad in self._deep_sink:
-            key = flat_ids.data_ptr()
-            mate = wide_by_ids.get(key)
-            if (not use_binned
-                    and mate is not None and flat_ids.is_cuda and ops.HAVE_EXT
+        deep_rule, wide_rule = (self.sparse_optimizer,
+                                self.wide_sparse_optimizer)
+        deep, wide = self.weight.data, self.wide_weight.data
+        both_sgd = not self._stateful()
+        both_stateful = "sgd" not in (deep_rule, wide_rule)
+        use_binned = (both_sgd and deep.is_cuda and self.dim == 16
+                      and ops.HAVE_EXT and bool(records)
+                      and self._binned_on(records[0].ids))
+        deep_ws = wide_ws = None
+        if both_stateful:
+            deep_ws = self._adagrad_workspace(deep, wide)
+            wide_ws = deep_ws.wide_view()
+        elif deep_rule != "sgd":
+            deep_ws = self._adagrad_workspace(deep)
+        elif wide_rule != "sgd":
+            wide_ws = self._adagrad_workspace(wide)
+        fan = self.F if self.world == 1 else self.f_own
+        for rec in records:
+            ids, deep_grad, wide_grad = rec.ids, rec.deep_grad, rec.wide_grad
+            if (both_sgd and not use_binned and ids.is_cuda and ops.HAVE_EXT
                     and self.dim % 4 == 0 and wide_lr == lr
-                    and grad.dtype == mate[1].dtype
-                    and mate[0] not in fused_wide_done):
-                # grad may be the strided slice backward stashed (W == 1)
+                    and deep_grad.dtype == wide_grad.dtype):
+                # deep_grad may be the strided slice backward kept (W == 1)
                 ops.emb_bwd_sgd_fused_wide(
-                    self.weight.data, self.wide_weight.data, flat_ids,
-                    grad, mate[1], lr=lr, scale=scale,
-                    offsets=self.full_offsets if key in raw_keys else None)
-                fused_wide_done.add(mate[0])
+                    deep, wide, ids, deep_grad, wide_grad, lr=lr,
+                    scale=scale,
+                    offsets=self.full_offsets if rec.raw_ids else None)
                 continue
-            flat_ids = flat_of(flat_ids)
+            if rec.raw_ids:  # did not get the fused kernel after all
+                ids = (ids + self.full_offsets.unsqueeze(0)).reshape(-1)
             # (a strided slice is gathered into a dense array here)
-            grad2d = grad.reshape(flat_ids.numel(), self.dim)
-            if use_binned:
-                ops.emb_bwd_sgd_binned(
-                    self.weight.data, flat_ids, grad2d,
-                    lr=lr, scale=scale, perm=perm_for(flat_ids))
+            grad2d = deep_grad.reshape(ids.numel(), self.dim)
+            if both_stateful:
+                ops.emb_bwd_sparse(
+                    ids,
+                    deep=self._sparse_side(deep_rule, "", deep, grad2d, lr),
+                    wide=self._sparse_side(wide_rule, "wide_", wide,
+                                           wide_grad, wide_lr),
+                    scale=scale, workspace=deep_ws)
+                continue
+            perm = self._record_perm(rec, ids) if use_binned else None
+            if deep_rule != "sgd":
+                self._sparse_apply_one(deep_rule, "", deep, ids, grad2d, lr,
+                                       scale, deep_ws, wide=False)
+            elif use_binned:
+                ops.emb_bwd_sgd_binned(deep, ids, grad2d, lr=lr,
+                                       scale=scale, perm=perm)
             else:
-                ops.emb_bwd_sgd(self.weight.data, flat_ids, grad2d,
-                                lr=lr, scale=scale)
-        self._deep_sink.clear()
-        for i, (flat_ids, gw) in enumerate(self._wide_sink):
-            if i in fused_wide_done:
-                continue
-            flat_ids = flat_of(flat_ids)
-            # gw layout [W, B] (or [B] local); ids layout [peer][b][j]
-            if use_binned:
-                ops.emb_scatter_sum_binned(
-                    self.wide_weight.data, flat_ids, gw,
-                    alpha=-wide_lr * scale, perm=perm_for(flat_ids))
-                continue
-            fan = self.F if self.world == 1 else self.f_own
-            ids2d = flat_ids.reshape(gw.numel(), fan)
-            ops.emb_scatter_sum(self.wide_weight.data, ids2d, gw,
-                                alpha=-wide_lr * scale)
-        self._wide_sink.clear()
-        raw_keys.clear()
+                ops.emb_bwd_sgd(deep, ids, grad2d, lr=lr, scale=scale)
+            # wide_grad layout [W, B] (or [B] local); ids [peer][b][j]
+            if wide_rule != "sgd":
+                self._sparse_apply_one(wide_rule, "wide_", wide, ids,
+                                       wide_grad, wide_lr, scale, wide_ws,
+                                       wide=True)
+            elif use_binned:
+                ops.emb_scatter_sum_binned(wide, ids, wide_grad,
+                                           alpha=-wide_lr * scale, perm=perm)
+            else:
+                ops.emb_scatter_sum(
+                    wide, ids.reshape(wide_grad.numel(), fan), wide_grad,
+                    alpha=-wide_lr * scale)
+        records.clear()
 
     def clear_pending(self) -> None:
-        self._deep_sink.clear()
-        self._wide_sink.clear()
-        self._raw_ids_keys.clear()
-        # matched to its ids by address: must not outlive them
-        self._pending_perm = None
+        self._pending.clear()

@@ -316,41 +316,55 @@ class BagUpdate(NamedTuple):
     """A sink entry that came from bags (``forward(..., bag_offsets=...)``):
     ``(flat_ids [nnz], grad_rows [nnz, dim])`` like every other entry, but
     ``nnz`` differs from rank to rank, so its data-parallel gather is the
-    padded one of :func:`_ragged_all_gather`."""
+    padded one of :func:`_all_gather_rows`."""
     flat_ids: torch.Tensor
     grad_rows: torch.Tensor
 
 
-def _ragged_all_gather(flat_ids: torch.Tensor, rows: torch.Tensor,
-                       world: int, process_group):
-    """Gather update lists whose length differs by rank.
+def _table_offsets(sizes: List[int]) -> torch.Tensor:
+    """int64 ``[len(sizes)]``: the first row of each table in the fused
+    one (``[0]`` for no table at all)."""
+    return torch.tensor([0] + list(sizes)[:-1], dtype=torch.int64).cumsum(0)
+
+
+def _all_gather_rows(flat_ids: torch.Tensor, rows: torch.Tensor,
+                     world: int, process_group, ragged: bool):
+    """Gather every rank's ``(flat_ids, rows)`` asynchronously.  Returns
+    ``(all_ids, all_rows, works, counts)``.
+
+    Equal lengths on every rank (``ragged=False``): two
+    ``all_gather_into_tensor``, no host sync, ``counts`` is None.
+
+    Lengths that differ by rank (``ragged=True``, one row per id):
     ``all_gather_into_tensor`` needs equal counts, so the per-rank counts
     are gathered first (one small collective and one ``.tolist()``, a host
     sync, per table and step), then ids and rows are zero-padded to the
-    maximum and gathered asynchronously.  Returns ``(all_ids, all_rows,
-    works, counts)``; :func:`_valid_prefixes` drops the padding again, so
-    it never reaches an update op."""
-    n = flat_ids.numel()
-    count = torch.tensor([n], dtype=torch.int64, device=flat_ids.device)
-    all_counts = torch.empty(world, dtype=torch.int64,
+    maximum.  :func:`_valid_prefixes` drops the padding again, so it never
+    reaches an update op."""
+    n_ids, n_rows, counts = flat_ids.numel(), rows.shape[0], None
+    if ragged:
+        count = torch.tensor([n_ids], dtype=torch.int64,
                              device=flat_ids.device)
-    dist.all_gather_into_tensor(all_counts, count, group=process_group)
-    counts = all_counts.tolist()
-    m = max(counts)
-    all_ids = torch.empty(m * world, dtype=flat_ids.dtype,
+        all_counts = torch.empty(world, dtype=torch.int64,
+                                 device=flat_ids.device)
+        dist.all_gather_into_tensor(all_counts, count, group=process_group)
+        counts = all_counts.tolist()
+        m = max(counts)
+        ids_p = flat_ids.new_zeros(m)
+        ids_p[:n_ids] = flat_ids
+        rows_p = rows.new_zeros((m,) + tuple(rows.shape[1:]))
+        rows_p[:n_ids] = rows
+        flat_ids, rows, n_ids, n_rows = ids_p, rows_p, m, m
+    all_ids = torch.empty(n_ids * world, dtype=flat_ids.dtype,
                           device=flat_ids.device)
-    all_rows = torch.empty((m * world,) + tuple(rows.shape[1:]),
+    all_rows = torch.empty((n_rows * world,) + tuple(rows.shape[1:]),
                            dtype=rows.dtype, device=rows.device)
-    if m == 0:
+    if ragged and n_ids == 0:
         return all_ids, all_rows, [], counts
-    ids_p = flat_ids.new_zeros(m)
-    ids_p[:n] = flat_ids
-    rows_p = rows.new_zeros((m,) + tuple(rows.shape[1:]))
-    rows_p[:n] = rows
     works = [
-        dist.all_gather_into_tensor(all_ids, ids_p, group=process_group,
+        dist.all_gather_into_tensor(all_ids, flat_ids, group=process_group,
                                     async_op=True),
-        dist.all_gather_into_tensor(all_rows, rows_p, group=process_group,
+        dist.all_gather_into_tensor(all_rows, rows, group=process_group,
                                     async_op=True),
     ]
     return all_ids, all_rows, works, counts
@@ -371,6 +385,90 @@ def _valid_prefixes(all_ids: torch.Tensor, all_rows: torch.Tensor,
                        for r, c in enumerate(counts)]))
 
 
+class _ReplicatedTable(SparseOptimizerMixin, nn.Module):
+    """What the two replicated embedding modules share: the fused table's
+    ``offsets``, the sink their backwards append ``(flat_ids, grad)`` to,
+    and its data-parallel sync.  A subclass says how a sink gradient
+    becomes update rows (:meth:`_update_rows`), how its table takes an SGD
+    update (:meth:`_sgd_update`) and whether it is the dim-1 wide table
+    (``_WIDE``)."""
+
+    _WIDE = False
+
+    def __init__(self, table_sizes: List[int]):
+        super().__init__()
+        self.table_sizes = list(table_sizes)
+        self.register_buffer("offsets", _table_offsets(table_sizes),
+                             persistent=True)
+        self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
+        self._pending_world = 1
+        self._gathered: List[tuple] = []
+
+    def pending_grads(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        return self._sink
+
+    @torch.no_grad()
+    def start_sparse_sync(self, process_group=None) -> None:
+        """Launch the cross-rank allgather of (ids, update rows)
+        asynchronously (overlaps with the dense optimizer step)."""
+        world = (dist.get_world_size(process_group)
+                 if dist.is_available() and dist.is_initialized() else 1)
+        self._pending_world = world
+        self._gathered = []
+        for entry in self._sink:
+            flat_ids, grad = entry
+            rows = self._update_rows(flat_ids, grad)
+            # nnz of a bag entry differs by rank: counts first (a host
+            # sync), then the padded gather
+            ragged = isinstance(entry, BagUpdate)
+            if world > 1:
+                self._gathered.append(_all_gather_rows(
+                    flat_ids, rows, world, process_group, ragged))
+            else:
+                # a bag entry carries its count, the mark that lets an
+                # all-empty one be skipped
+                self._gathered.append((
+                    flat_ids, rows, [],
+                    [flat_ids.numel()] if ragged else None))
+        self._sink.clear()
+
+    @torch.no_grad()
+    def finish_sparse_sync(self, lr: float) -> None:
+        """Wait for the allgathers and apply the table's update (fused
+        scatter+SGD, or its stateful rule) scaled by 1/world_size."""
+        world = self._pending_world
+        if self.wide_sparse_lr is not None:
+            lr = self.wide_sparse_lr
+        for all_ids, all_rows, works, counts in self._gathered:
+            for w in works:
+                w.wait()
+            all_ids, all_rows = _valid_prefixes(all_ids, all_rows, counts)
+            if counts is not None and all_ids.numel() == 0:
+                continue  # every bag on every rank was empty
+            if self.sparse_optimizer != "sgd":
+                self._sparse_apply_one(
+                    self.sparse_optimizer, "", self.weight.data, all_ids,
+                    all_rows, lr, 1.0 / world,
+                    self._adagrad_workspace(self.weight.data),
+                    wide=self._WIDE)
+                continue
+            self._sgd_update(all_ids, all_rows, lr, world)
+        self._gathered = []
+
+    @torch.no_grad()
+    def apply_sparse_updates(self, lr: float, process_group=None) -> None:
+        """Allgather sparse grads across DP ranks and apply the table's
+        update, scaled by 1/world_size."""
+        if not self._sink:
+            return
+        self.start_sparse_sync(process_group)
+        self.finish_sparse_sync(lr)
+
+    def clear_pending(self) -> None:
+        self._sink.clear()
+        self._gathered = []
+
+
 class _FusedLookup(torch.autograd.Function):
     """Gather via the HIP kernel; backward stashes sparse (ids, grad)."""
 
@@ -388,7 +486,7 @@ class _FusedLookup(torch.autograd.Function):
         return None, None, None, None
 
 
-class SparseEmbedding(SparseOptimizerMixin, nn.Module):
+class SparseEmbedding(_ReplicatedTable):
     """Fused multi-table embedding with sparse-allgather DP sync.
 
     ``forward(ids [B, F])`` -> ``[B, F*dim]``.  Multi-hot features:
@@ -416,16 +514,11 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
                  sparse_betas: Tuple[float, float] = (0.9, 0.999),
                  combiner: str = "sum"):
-        super().__init__()
-        self.table_sizes = list(table_sizes)
+        super().__init__(table_sizes)
         self.dim = dim
         self.combiner = _check_combiner(combiner)
         self.out_bf16 = out_bf16
         total = sum(table_sizes)
-        offsets = torch.tensor(
-            [0] + list(torch.cumsum(torch.tensor(table_sizes), 0)[:-1]),
-            dtype=torch.int64)
-        self.register_buffer("offsets", offsets, persistent=True)
         std = init_std if init_std is not None else 1.0 / math.sqrt(dim)
         weight = torch.randn(total, dim) * std
         self.weight = nn.Parameter(weight)
@@ -437,7 +530,6 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
             {"": (self.weight, sparse_optimizer)},
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
             sparse_betas=sparse_betas)
-        self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor,
                 bag_offsets: Optional[torch.Tensor] = None,
@@ -454,85 +546,12 @@ class SparseEmbedding(SparseOptimizerMixin, nn.Module):
                                  self._sink)
         return out.reshape(b, f * self.dim)
 
-    def pending_grads(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
-        return self._sink
+    def _update_rows(self, flat_ids, grad) -> torch.Tensor:
+        return grad.reshape(flat_ids.numel(), self.dim)
 
-    @torch.no_grad()
-    def start_sparse_sync(self, process_group=None) -> None:
-        """Launch the cross-rank allgather of (ids, grad rows)
-        asynchronously (overlaps with the dense optimizer step)."""
-        world = (dist.get_world_size(process_group)
-                 if dist.is_available() and dist.is_initialized() else 1)
-        self._pending_world = world
-        self._gathered: List[tuple] = []
-        for entry in self._sink:
-            flat_ids, grad = entry
-            grad2d = grad.reshape(flat_ids.numel(), self.dim)
-            if world > 1 and isinstance(entry, BagUpdate):
-                # nnz differs by rank: counts first (a host sync), then
-                # the padded gather
-                self._gathered.append(_ragged_all_gather(
-                    flat_ids, grad2d, world, process_group))
-            elif world > 1:
-                n = flat_ids.numel()
-                all_ids = torch.empty(n * world, dtype=flat_ids.dtype,
-                                      device=flat_ids.device)
-                all_grads = torch.empty((n * world, self.dim),
-                                        dtype=grad2d.dtype,
-                                        device=grad2d.device)
-                works = [
-                    dist.all_gather_into_tensor(all_ids, flat_ids,
-                                                group=process_group,
-                                                async_op=True),
-                    dist.all_gather_into_tensor(all_grads, grad2d,
-                                                group=process_group,
-                                                async_op=True),
-                ]
-                self._gathered.append((all_ids, all_grads, works, None))
-            else:
-                # a bag entry carries its count, the mark that lets an
-                # all-empty one be skipped
-                self._gathered.append((
-                    flat_ids, grad2d, [],
-                    [flat_ids.numel()] if isinstance(entry, BagUpdate)
-                    else None))
-        self._sink.clear()
-
-    @torch.no_grad()
-    def finish_sparse_sync(self, lr: float) -> None:
-        """Wait for the allgathers and apply the fused scatter+SGD (or
-        sparse Adagrad) update scaled by 1/world_size."""
-        world = getattr(self, "_pending_world", 1)
-        for all_ids, all_grads, works, counts in getattr(self, "_gathered",
-                                                         []):
-            for w in works:
-                w.wait()
-            all_ids, all_grads = _valid_prefixes(all_ids, all_grads, counts)
-            if counts is not None and all_ids.numel() == 0:
-                continue  # every bag on every rank was empty
-            if self.sparse_optimizer != "sgd":
-                self._sparse_apply_one(
-                    self.sparse_optimizer, "", self.weight.data, all_ids,
-                    all_grads, lr, 1.0 / world,
-                    self._adagrad_workspace(self.weight.data), wide=False)
-                continue
-            ops.emb_bwd_sgd(self.weight.data, all_ids, all_grads,
-                            lr=lr, scale=1.0 / world)
-        self._gathered = []
-
-    @torch.no_grad()
-    def apply_sparse_updates(self, lr: float,
-                             process_group=None) -> None:
-        """Allgather sparse grads across DP ranks and apply the fused
-        scatter+SGD update, scaled by 1/world_size."""
-        if not self._sink:
-            return
-        self.start_sparse_sync(process_group)
-        self.finish_sparse_sync(lr)
-
-    def clear_pending(self) -> None:
-        self._sink.clear()
-        self._gathered = []
+    def _sgd_update(self, ids, rows, lr: float, world: int) -> None:
+        ops.emb_bwd_sgd(self.weight.data, ids, rows, lr=lr,
+                        scale=1.0 / world)
 
 
 class _GatherSum(torch.autograd.Function):
@@ -553,7 +572,7 @@ class _GatherSum(torch.autograd.Function):
         return None, None, None, None, None
 
 
-class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
+class WideScalarEmbedding(_ReplicatedTable):
     """Per-id scalar weights with fused gather-sum forward and
     scatter-add sparse update (the wide part of wide-and-deep);
     ``sparse_optimizer="adagrad"`` switches the update to sparse
@@ -576,15 +595,10 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
                  wide_sparse_lr: Optional[float] = None,
                  sparse_betas: Tuple[float, float] = (0.9, 0.999),
                  combiner: str = "sum"):
-        super().__init__()
-        self.table_sizes = list(table_sizes)
+        super().__init__(table_sizes)
         self.out_bf16 = out_bf16
         self.combiner = _check_combiner(combiner)
         total = sum(table_sizes)
-        offsets = torch.tensor(
-            [0] + list(torch.cumsum(torch.tensor(table_sizes), 0)[:-1]),
-            dtype=torch.int64)
-        self.register_buffer("offsets", offsets, persistent=True)
         self.weight = nn.Parameter(torch.randn(total, 1) * init_std)
         self.weight._miyarn_sparse = True
         self.sparse_optimizer = _check_sparse_rule("sparse_optimizer",
@@ -594,7 +608,6 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
             {"": (self.weight, sparse_optimizer)},
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
             wide_sparse_lr=wide_sparse_lr, sparse_betas=sparse_betas)
-        self._sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
     def forward(self, ids: torch.Tensor,
                 bag_offsets: Optional[torch.Tensor] = None,
@@ -618,77 +631,15 @@ class WideScalarEmbedding(SparseOptimizerMixin, nn.Module):
         flat_ids, rows = entry
         return BagUpdate(flat_ids, rows.reshape(-1))  # [nnz, 1] -> [nnz]
 
-    def pending_grads(self):
-        return self._sink
+    _WIDE = True
 
-    @torch.no_grad()
-    def start_sparse_sync(self, process_group=None) -> None:
-        world = (dist.get_world_size(process_group)
-                 if dist.is_available() and dist.is_initialized() else 1)
-        self._pending_world = world
-        self._gathered = []
-        for entry in self._sink:
-            flat_ids, grad = entry
-            if world > 1 and isinstance(entry, BagUpdate):
-                self._gathered.append(_ragged_all_gather(
-                    flat_ids, grad.reshape(-1), world, process_group))
-            elif world > 1:
-                n = flat_ids.numel()
-                b = grad.numel()
-                all_ids = torch.empty(n * world, dtype=flat_ids.dtype,
-                                      device=flat_ids.device)
-                all_grads = torch.empty(b * world, dtype=grad.dtype,
-                                        device=grad.device)
-                works = [
-                    dist.all_gather_into_tensor(all_ids, flat_ids,
-                                                group=process_group,
-                                                async_op=True),
-                    dist.all_gather_into_tensor(all_grads,
-                                                grad.reshape(-1),
-                                                group=process_group,
-                                                async_op=True),
-                ]
-                self._gathered.append((all_ids, all_grads, works, None))
-            else:
-                self._gathered.append((
-                    flat_ids, grad.reshape(-1), [],
-                    [flat_ids.numel()] if isinstance(entry, BagUpdate)
-                    else None))
-        self._sink.clear()
+    def _update_rows(self, flat_ids, grad) -> torch.Tensor:
+        return grad.reshape(-1)  # one per example, or per id from bags
 
-    @torch.no_grad()
-    def finish_sparse_sync(self, lr: float) -> None:
-        world = getattr(self, "_pending_world", 1)
-        if self.wide_sparse_lr is not None:
-            lr = self.wide_sparse_lr
-        for all_ids, all_grads, works, counts in getattr(self, "_gathered",
-                                                         []):
-            for w in works:
-                w.wait()
-            all_ids, all_grads = _valid_prefixes(all_ids, all_grads, counts)
-            if counts is not None and all_ids.numel() == 0:
-                continue
-            if self.sparse_optimizer != "sgd":
-                self._sparse_apply_one(
-                    self.sparse_optimizer, "", self.weight.data, all_ids,
-                    all_grads, lr, 1.0 / world,
-                    self._adagrad_workspace(self.weight.data), wide=True)
-                continue
-            ops.emb_scatter_sum(self.weight.data,
-                                all_ids.reshape(all_grads.numel(), -1),
-                                all_grads, alpha=-lr / world)
-        self._gathered = []
-
-    @torch.no_grad()
-    def apply_sparse_updates(self, lr: float, process_group=None) -> None:
-        if not self._sink:
-            return
-        self.start_sparse_sync(process_group)
-        self.finish_sparse_sync(lr)
-
-    def clear_pending(self) -> None:
-        self._sink.clear()
-        self._gathered = []
+    def _sgd_update(self, ids, rows, lr: float, world: int) -> None:
+        ops.emb_scatter_sum(self.weight.data,
+                            ids.reshape(rows.numel(), -1), rows,
+                            alpha=-lr / world)
 
 
 class _DeepInput(torch.autograd.Function):
