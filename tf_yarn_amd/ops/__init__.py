@@ -1349,6 +1349,107 @@ class EmbeddingBagFn(torch.autograd.Function):
         return (None,) * 12
 
 
+# ---- pairwise dot feature interaction (DLRM) -------------------------------
+
+def dot_interaction_width(n_features: int, dim: int) -> int:
+    """Columns of :func:`dot_interaction`'s result: ``dim`` pass-through
+    columns and the ``N*(N-1)/2`` pairs of ``N = n_features + 1`` vectors,
+    rounded up to a multiple of 16 (the next layer's GEMMs need
+    ``K % 16 == 0``)."""
+    n = n_features + 1
+    return -(-(dim + n * (n - 1) // 2) // 16) * 16
+
+
+def dot_interaction_enabled() -> bool:
+    """MIYARN_DOT_INTERACTION=0 sends bf16 GPU operands through the torch
+    composition too."""
+    return _env_switch_on("MIYARN_DOT_INTERACTION")
+
+
+def dot_interaction_kernel_ok(dense_vec: torch.Tensor,
+                              emb: torch.Tensor) -> bool:
+    """True when :func:`dot_interaction` runs the HIP kernels
+    (``csrc/dot_interaction.hip``) for these operands: bf16 on one GPU,
+    ``N = F + 1 <= 32``, ``D % 16 == 0``, ``D <= 128``, unit column stride,
+    row strides that are multiples of 8 elements and 16-byte aligned
+    bases."""
+    return (HAVE_EXT and dense_vec.is_cuda and emb.is_cuda
+            and dot_interaction_enabled()
+            and _C.dot_interaction_ok(dense_vec, emb))
+
+
+@functools.lru_cache(maxsize=None)
+def _tril_pairs(n: int, device: torch.device):
+    """Row and column indices of the strictly lower triangle, row-major."""
+    i, j = torch.tril_indices(n, n, offset=-1, device=device)
+    return i, j
+
+
+def _dot_interaction_ref(dense_vec: torch.Tensor,
+                         emb: torch.Tensor) -> torch.Tensor:
+    """The composition: ``bmm``, a gather of the triangle, ``cat`` with the
+    pad.  bf16 operands are multiplied and summed in fp32 and rounded
+    once."""
+    b, d = dense_vec.shape
+    n = emb.shape[1] // d + 1
+    tf = torch.cat([dense_vec, emb], dim=1).reshape(b, n, d).float()
+    i, j = _tril_pairs(n, dense_vec.device)
+    pairs = torch.bmm(tf, tf.transpose(1, 2))[:, i, j]
+    pad = dot_interaction_width(n - 1, d) - d - pairs.shape[1]
+    # the whole row is rounded once, so autograd rounds each gradient once
+    return torch.cat([tf[:, 0], pairs, pairs.new_zeros(b, pad)],
+                     dim=1).to(dense_vec.dtype)
+
+
+class DotInteractionFn(torch.autograd.Function):
+    """``out [B, W] = dot_interaction(dense_vec [B, D], emb [B, F*D])``.
+    With ``T[b]`` the ``[N, D]`` matrix of ``dense_vec[b]`` and the ``F``
+    embedding vectors, ``N = F + 1``, ``P = N*(N-1)/2``::
+
+        out[b, c]                 = dense_vec[b, c]               c < D
+        out[b, D + i*(i-1)/2 + j] = sum_k T[b,i,k] * T[b,j,k]     j < i < N
+        out[b, D + P .. W-1]      = 0
+
+    and backward ``dT[b] = S[b] @ T[b]`` with ``S`` the symmetric matrix of
+    the pair gradients (zero diagonal), ``d_dense_vec`` also taking the
+    pass-through columns' gradient.  Where
+    :func:`dot_interaction_kernel_ok` holds, forward and backward are one
+    HIP kernel each; every other case (the CPU, fp32, shapes and layouts
+    the kernels refuse) is the torch composition."""
+
+    @staticmethod
+    def forward(ctx, dense_vec, emb):
+        ctx.kernel = dot_interaction_kernel_ok(dense_vec, emb)
+        ctx.save_for_backward(dense_vec, emb)
+        if ctx.kernel:
+            return _C.dot_interaction_fwd(dense_vec, emb)
+        if _on_gpu(dense_vec, emb):
+            _require_ext()
+        return _dot_interaction_ref(dense_vec, emb)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dense_vec, emb = ctx.saved_tensors
+        if ctx.kernel:
+            if not (grad_out.stride(1) == 1 and grad_out.stride(0) % 8 == 0
+                    and grad_out.data_ptr() % 16 == 0):
+                grad_out = grad_out.contiguous()
+            d_dense, d_emb = _C.dot_interaction_bwd(grad_out, dense_vec, emb)
+            return d_dense, d_emb
+        with torch.enable_grad():
+            dv = dense_vec.detach().requires_grad_()
+            e = emb.detach().requires_grad_()
+            out = _dot_interaction_ref(dv, e)
+        return torch.autograd.grad(out, (dv, e), grad_out)
+
+
+def dot_interaction(dense_vec: torch.Tensor,
+                    emb: torch.Tensor) -> torch.Tensor:
+    """DLRM's pairwise dot interaction without self-interaction
+    (:class:`DotInteractionFn`)."""
+    return DotInteractionFn.apply(dense_vec, emb)
+
+
 def col_reduce_dot(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     """dw[m] = sum_b dy[b] * x[b, m] (fp32 result)."""
     if _on_gpu(x, dy):

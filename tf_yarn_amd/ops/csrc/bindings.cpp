@@ -76,6 +76,15 @@ torch::Tensor emb_bag_bwd_rows(torch::Tensor grad_out,
                                c10::optional<torch::Tensor> weights,
                                int64_t col_offset);
 
+// dot_interaction.hip
+bool dot_interaction_ok(torch::Tensor dense_vec, torch::Tensor emb);
+torch::Tensor dot_interaction_fwd(torch::Tensor dense_vec, torch::Tensor emb,
+                                  int64_t max_blocks);
+std::vector<torch::Tensor> dot_interaction_bwd(torch::Tensor grad_out,
+                                               torch::Tensor dense_vec,
+                                               torch::Tensor emb,
+                                               int64_t max_blocks);
+
 // sparse_adagrad.hip
 // one table's side of a stateful sparse update: (rule name, table, state
 // tensors, accumulator, gradient or None, lr, eps, l1, l2); a lazy_adam
@@ -203,6 +212,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grad_out"), py::arg("bag_offsets"), py::arg("bag_scale"),
         py::arg("dim"), py::arg("n_features"), py::arg("nnz"),
         py::arg("weights"), py::arg("col_offset"));
+  m.def("dot_interaction_ok", &dot_interaction_ok,
+        "True when the dot-interaction kernels take these operands",
+        py::arg("dense_vec"), py::arg("emb"));
+  m.def("dot_interaction_fwd", &dot_interaction_fwd,
+        "Pairwise dot interaction [B, W]: dense_vec, the packed strictly "
+        "lower triangle of T T^T, zero pad; max_blocks caps the grid "
+        "(0: the normal cap)",
+        py::arg("dense_vec"), py::arg("emb"), py::arg("max_blocks") = 0);
+  m.def("dot_interaction_bwd", &dot_interaction_bwd,
+        "Both input gradients of dot_interaction_fwd in one kernel; returns "
+        "(d_dense_vec, d_emb)",
+        py::arg("grad_out"), py::arg("dense_vec"), py::arg("emb"),
+        py::arg("max_blocks") = 0);
   m.def("emb_bwd_dense", &emb_bwd_dense,
         "Sparse embedding grad scatter into dense grad table");
   m.def("emb_bwd_sparse", &emb_bwd_sparse,
