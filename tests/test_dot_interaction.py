@@ -25,6 +25,78 @@ def test_composition_matches_definition(n, d, dtype):
         assert a.dtype == dtype and torch.equal(a, b)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("n,d", [(27, 16), (32, 48)])
+def test_composition_rounds_like_the_definition(n, d, dtype):
+    """Operands in [-16, 16]: fp32 is still exact in any order, and a
+    quarter to a half of the values need a real rounding to bf16."""
+    dv, emb, g = (t.to(dtype) for t in R.int_operands(3, n, d, seed=1,
+                                                      amax=16))
+    ref = R.ref64(dv, emb, g)
+    want = [t.float().to(dtype) for t in ref]
+    if dtype == torch.bfloat16:
+        assert all((w.double() != r).any() for w, r in zip(want, ref))
+    dv.requires_grad_()
+    emb.requires_grad_()
+    out = ops.dot_interaction(dv, emb)
+    got = [out, *torch.autograd.grad(out, (dv, emb), g)]
+    for a, b in zip(got, want):
+        assert a.dtype == dtype and torch.equal(a, b)
+
+
+def _composition(dv, emb, g):
+    dv = dv.clone().requires_grad_()
+    emb = emb.clone().requires_grad_()
+    out = ops.dot_interaction(dv, emb)
+    return [out.detach(), *torch.autograd.grad(out, (dv, emb), g)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("where", ["emb", "grad_out"])
+def test_composition_keeps_non_finite_values_in_their_example(where, dtype):
+    """One +Inf and one NaN in ``emb[1]``, or Infs and a NaN in
+    ``grad_out[1]``.  Every other example is bit-identical to the clean
+    run, and the forward equals the definition, NaN for NaN.
+
+    The backward of the poisoned example equals the definition when the
+    poison is in ``grad_out``.  With the poison in ``emb`` it does NOT: the
+    definition sums ``S[i][k] * T[k][c]`` over k, so a non-finite
+    ``T[k][c]`` gives NaN where ``S[i][k] == 0`` (the diagonal included) and
+    a signed Inf elsewhere.  Autograd's backward of ``bmm`` plus triangle
+    gather computes ``L @ T + L^T @ T`` with ``L`` the strictly lower
+    triangle of ``S``, so every row i meets the structural zero ``L[i][k]``
+    or ``L^T[i][k]`` of every k: a column c of ``T`` that holds a
+    non-finite value is NaN in EVERY row of both gradients, where the
+    definition (and the HIP kernel) has Infs too.  Columns without poison
+    equal the definition bit for bit.  That is what is asserted."""
+    n, d, b = 27, 16, 9
+    dv, emb, g = (t.to(dtype) for t in R.int_operands(b, n, d, seed=5))
+    clean = _composition(dv, emb, g)
+    if where == "emb":
+        emb = R.poison_emb(emb, d)
+    else:
+        g = R.poison_grad(g, d)
+    want = [t.float().to(dtype) for t in R.ref64(dv, emb, g)]
+    got = _composition(dv, emb, g)
+    others = [i for i in range(b) if i != 1]
+    for a, c, w in zip(got, clean, want):
+        assert torch.equal(a[others], c[others])
+        assert torch.equal(a[others], w[others])
+    assert R.same_bits(got[0], want[0])
+    assert not want[1][1].isfinite().all() and not want[2][1].isfinite().all()
+    if where == "grad_out":
+        assert R.same_bits(got[1], want[1]) and R.same_bits(got[2], want[2])
+        return
+    t1 = torch.cat([dv[1:2], emb[1].reshape(n - 1, d)])
+    bad = ~t1.isfinite().all(0)  # the columns of T that hold the poison
+    assert bad.sum() == 2
+    dt_got = torch.cat([got[1][1:2], got[2][1].reshape(n - 1, d)])
+    dt_want = torch.cat([want[1][1:2], want[2][1].reshape(n - 1, d)])
+    assert torch.equal(dt_got[:, ~bad], dt_want[:, ~bad])
+    assert dt_got[:, bad].isnan().all()
+    assert dt_want[:, bad].isinf().any()  # the difference is real
+
+
 def test_width():
     assert ops.dot_interaction_width(26, 16) == 368
     assert ops.dot_interaction_width(1, 16) == 32

@@ -1431,9 +1431,13 @@ class DotInteractionFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         dense_vec, emb = ctx.saved_tensors
         if ctx.kernel:
-            if not (grad_out.stride(1) == 1 and grad_out.stride(0) % 8 == 0
-                    and grad_out.data_ptr() % 16 == 0):
-                grad_out = grad_out.contiguous()
+            # the binding's own layout test: what it would refuse (an
+            # expanded grad_out of a sum over the batch, an odd offset) is
+            # copied, what it takes is read where it lies.  clone, not
+            # contiguous(): dense rows at an odd offset ARE contiguous
+            if not _C.dot_interaction_grad_ok(grad_out):
+                grad_out = grad_out.clone(
+                    memory_format=torch.contiguous_format)
             d_dense, d_emb = _C.dot_interaction_bwd(grad_out, dense_vec, emb)
             return d_dense, d_emb
         with torch.enable_grad():

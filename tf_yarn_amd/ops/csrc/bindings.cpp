@@ -78,6 +78,7 @@ torch::Tensor emb_bag_bwd_rows(torch::Tensor grad_out,
 
 // dot_interaction.hip
 bool dot_interaction_ok(torch::Tensor dense_vec, torch::Tensor emb);
+bool dot_interaction_grad_ok(torch::Tensor grad_out);
 torch::Tensor dot_interaction_fwd(torch::Tensor dense_vec, torch::Tensor emb,
                                   int64_t max_blocks);
 std::vector<torch::Tensor> dot_interaction_bwd(torch::Tensor grad_out,
@@ -215,6 +216,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dot_interaction_ok", &dot_interaction_ok,
         "True when the dot-interaction kernels take these operands",
         py::arg("dense_vec"), py::arg("emb"));
+  m.def("dot_interaction_grad_ok", &dot_interaction_grad_ok,
+        "True when dot_interaction_bwd reads this grad_out in place",
+        py::arg("grad_out"));
   m.def("dot_interaction_fwd", &dot_interaction_fwd,
         "Pairwise dot interaction [B, W]: dense_vec, the packed strictly "
         "lower triangle of T T^T, zero pad; max_blocks caps the grid "

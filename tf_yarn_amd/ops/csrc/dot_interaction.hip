@@ -284,7 +284,8 @@ dot_interaction_bwd_kernel(const unsigned short* __restrict__ g,
 }
 
 // [B, cols] bf16 with unit column stride, rows a multiple of 8 elements
-// apart and a 16 B aligned base: what the 16 B loads need.
+// and at least their own width apart (no expanded or overlapping rows) and
+// a 16 B aligned base: what the 16 B loads need.
 bool rows_vector_ok(const torch::Tensor& t) {
   return t.dim() == 2 && t.scalar_type() == torch::kBFloat16 &&
          (t.size(1) <= 1 || t.stride(1) == 1) &&
@@ -349,6 +350,12 @@ bool dot_interaction_ok(torch::Tensor dense_vec, torch::Tensor emb) {
          shape_ok(emb.size(1) / dim, dim);
 }
 
+// True when dot_interaction_bwd reads this grad_out in place: the layout
+// test of its TORCH_CHECK, for the caller that would rather copy than raise.
+bool dot_interaction_grad_ok(torch::Tensor grad_out) {
+  return grad_out.is_cuda() && rows_vector_ok(grad_out);
+}
+
 torch::Tensor dot_interaction_fwd(torch::Tensor dense_vec, torch::Tensor emb,
                                   int64_t max_blocks) {
   check_operands(dense_vec, emb);
@@ -385,7 +392,8 @@ std::vector<torch::Tensor> dot_interaction_bwd(torch::Tensor grad_out,
               "grad_out must be [B, W] = [", B, ", ", W, "] on emb's GPU");
   TORCH_CHECK(rows_vector_ok(grad_out),
               "grad_out must be bf16 with unit column stride, a row stride "
-              "that is a multiple of 8 elements and a 16-byte aligned base");
+              "that is a multiple of 8 elements and no less than W, and a "
+              "16-byte aligned base");
   auto d_dense = torch::empty({B, D}, dense_vec.options());
   auto d_emb = torch::empty({B, emb.size(1)}, emb.options());
   const int grid = di_grid(B, max_blocks);
