@@ -1776,6 +1776,88 @@ def linear_bias_relu(x: torch.Tensor, weight: torch.Tensor,
 
 # ---- last hidden layer + single-logit head ---------------------------------
 
+# ---- cross layer (DCN-v2) --------------------------------------------------
+
+def _cross_layer_mode() -> str:
+    """MIYARN_CROSS_LAYER: ``0`` (or empty) sends every operand through the
+    torch composition; ``custom`` and anything else run the HIP kernels."""
+    v = os.environ.get("MIYARN_CROSS_LAYER", "1")
+    return "off" if v in ("", "0") else v
+
+
+def cross_layer_kernel_ok(x0: torch.Tensor, x: torch.Tensor,
+                          weight: torch.Tensor, bias: torch.Tensor) -> bool:
+    """True when :func:`cross_layer` runs the HIP kernels
+    (``csrc/cross_layer.hip``) for these operands: all bf16 on one GPU,
+    ``D % 16 == 0``, ``16 <= D <= 1024``, ``weight [D, D]`` and ``bias [D]``
+    contiguous, ``x0`` and ``x`` with unit column stride, row strides that
+    are multiples of 8 elements and 16-byte aligned bases."""
+    return (HAVE_EXT and x0.is_cuda and x.is_cuda and weight.is_cuda
+            and bias.is_cuda and _cross_layer_mode() != "off"
+            and _C.cross_layer_ok(x0, x, weight, bias))
+
+
+def _cross_layer_ref(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
+                     bias: torch.Tensor) -> torch.Tensor:
+    """The composition: products and sums in fp32, the result cast once, so
+    autograd rounds each gradient once too."""
+    xf = x.float()
+    v = xf.matmul(weight.float().t()) + bias.float()
+    return (x0.float() * v + xf).to(x.dtype)
+
+
+class CrossLayerFn(torch.autograd.Function):
+    """``y = x0 * (x @ weight.T + bias) + x`` (docs/Kernels.md, "Cross
+    layer").  Where :func:`cross_layer_kernel_ok` holds the forward is one
+    MFMA kernel (``_C.cross_fwd``) and the backward ``_C.cross_bwd_pre``
+    (``dz = g * x0``, ``dx0 = g * v`` and ``dbias`` in one pass) followed by
+    the two GEMMs on the linear layers' paths; every other case (the CPU,
+    fp32, shapes and layouts the kernels refuse, ``MIYARN_CROSS_LAYER=0``)
+    is the torch composition."""
+
+    @staticmethod
+    def forward(ctx, x0, x, weight, bias, save_v):
+        ctx.kernel = cross_layer_kernel_ok(x0, x, weight, bias)
+        if ctx.kernel:
+            y, v = _C.cross_fwd(x0, x, weight, bias, save_v)
+            ctx.save_for_backward(x0, x, weight, v)
+            return y
+        if _on_gpu(x0, x, weight, bias):
+            _require_ext()
+        ctx.save_for_backward(x0, x, weight, bias)
+        return _cross_layer_ref(x0, x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kernel:
+            x0, x, weight, v = ctx.saved_tensors
+            # what the binding would refuse (the expanded grad of a sum
+            # over the batch, an odd offset) is copied; clone, not
+            # contiguous(): dense rows at an odd offset ARE contiguous
+            if not _C.cross_rows_ok(g):
+                g = g.clone(memory_format=torch.contiguous_format)
+            dz, dx0, dbias = _C.cross_bwd_pre(g, x0, v)
+            # the library adds g in its epilogue and rounds once
+            dx = torch.addmm(g, dz, weight)
+            return dx0, dx, _linear_wgrad(dz, x, weight), dbias, None
+        x0, x, weight, bias = ctx.saved_tensors
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_()
+                      for t in (x0, x, weight, bias)]
+            y = _cross_layer_ref(*leaves)
+        return (*torch.autograd.grad(y, leaves, g), None)
+
+
+def cross_layer(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
+                bias: torch.Tensor) -> torch.Tensor:
+    """One DCN-v2 cross layer, ``x0 * (x @ weight.T + bias) + x``
+    (:class:`CrossLayerFn`).  The kernel saves ``v`` for the backward only
+    if some input needs a gradient: inference writes no ``v``."""
+    save_v = torch.is_grad_enabled() and any(
+        t.requires_grad for t in (x0, x, weight, bias))
+    return CrossLayerFn.apply(x0, x, weight, bias, save_v)
+
+
 def fused_head_bwd_enabled() -> bool:
     """MIYARN_FUSED_HEAD_BWD=0 restores the separate last layer and head
     (the head's backward materialises its ``[B, width]`` input gradient)."""

@@ -169,6 +169,16 @@ torch::Tensor gemm_bt(torch::Tensor a, torch::Tensor b,
 std::vector<torch::Tensor> dgrad_drelu(torch::Tensor dz_next, torch::Tensor w,
                                        torch::Tensor y, bool dbias_bf16);
 
+// cross_layer.hip
+bool cross_layer_ok(torch::Tensor x0, torch::Tensor x, torch::Tensor weight,
+                    torch::Tensor bias);
+bool cross_rows_ok(torch::Tensor t);
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> cross_fwd(
+    torch::Tensor x0, torch::Tensor x, torch::Tensor weight,
+    torch::Tensor bias, bool save_v);
+std::vector<torch::Tensor> cross_bwd_pre(torch::Tensor g, torch::Tensor x0,
+                                         torch::Tensor v);
+
 // eval_metrics.hip
 void binary_eval_update(torch::Tensor logits, torch::Tensor labels,
                         torch::Tensor hist, torch::Tensor counts,
@@ -318,6 +328,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "below and its dbias in the epilogue (returns [dz, dbias])",
         py::arg("dz_next"), py::arg("w"), py::arg("y"),
         py::arg("dbias_bf16") = false);
+  m.def("cross_layer_ok", &cross_layer_ok,
+        "True when the cross-layer kernels take these operands",
+        py::arg("x0"), py::arg("x"), py::arg("weight"), py::arg("bias"));
+  m.def("cross_rows_ok", &cross_rows_ok,
+        "True when the cross-layer kernels read these [B, D] rows in place",
+        py::arg("t"));
+  m.def("cross_fwd", &cross_fwd,
+        "Cross layer y = x0 * (x @ W^T + b) + x in one MFMA kernel; returns "
+        "(y, v) with v = bf16(x @ W^T + b) when save_v, else (y, None)",
+        py::arg("x0"), py::arg("x"), py::arg("weight"), py::arg("bias"),
+        py::arg("save_v"));
+  m.def("cross_bwd_pre", &cross_bwd_pre,
+        "Elementwise front of the cross layer's backward in one pass; "
+        "returns (dz = g * x0, dx0 = g * v, dbias = column sums of dz)",
+        py::arg("g"), py::arg("x0"), py::arg("v"));
   m.def("binary_eval_update", &binary_eval_update,
         "Fold a batch of (logit, label) into the streaming binary eval "
         "state: score histogram [2, 4096], counts (n_valid, n_nan, tp, fp), "
