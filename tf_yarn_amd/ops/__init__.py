@@ -1858,6 +1858,120 @@ def cross_layer(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
     return CrossLayerFn.apply(x0, x, weight, bias, save_v)
 
 
+# ---- field self-attention (AutoInt) ----------------------------------------
+
+def field_attention_enabled() -> bool:
+    """MIYARN_FIELD_ATTENTION=0 sends bf16 GPU operands through the torch
+    composition too."""
+    return _env_switch_on("MIYARN_FIELD_ATTENTION")
+
+
+def field_attention_kernel_ok(qkv: torch.Tensor, n_fields: int,
+                              n_heads: int) -> bool:
+    """True when :func:`field_attention` runs the HIP kernels
+    (``csrc/field_attention.hip``): bf16 ``qkv [B*N, 3*H*d]`` on one GPU,
+    ``1 <= N <= 32``, ``d`` in {16, 32, 64}, ``H*d <= 256``, unit column
+    stride, a row stride that is a multiple of 8 elements and at least
+    ``3*H*d``, and a 16-byte aligned base."""
+    return (HAVE_EXT and qkv.is_cuda and field_attention_enabled()
+            and _C.field_attention_ok(qkv, n_fields, n_heads))
+
+
+def _field_attention_parts(qkv, n_fields, n_heads, scale):
+    """fp32 ``q, k, v [B, H, N, d]`` and the attention matrix ``Pb
+    [B, H, N, N]``, rounded ONCE to ``qkv``'s dtype."""
+    rows, cols = qkv.shape
+    if (n_fields < 1 or n_heads < 1 or rows % n_fields
+            or cols % (3 * n_heads)):
+        raise ValueError(
+            f"qkv {tuple(qkv.shape)} is not [B*{n_fields}, 3*{n_heads}*d]")
+    d = cols // (3 * n_heads)
+    q, k, v = (qkv.reshape(-1, n_fields, 3, n_heads, d).float()
+               .permute(2, 0, 3, 1, 4))
+    p = torch.softmax(scale * q.matmul(k.transpose(-1, -2)), dim=-1)
+    return q, k, v, p.to(qkv.dtype).float()
+
+
+def _field_attention_ref(qkv: torch.Tensor, n_fields: int, n_heads: int,
+                         scale: float) -> torch.Tensor:
+    """The composition: fp32 ``bmm``, fp32 softmax, one cast of the
+    attention matrix, ``bmm``, one cast."""
+    _, _, v, pb = _field_attention_parts(qkv, n_fields, n_heads, scale)
+    return pb.matmul(v).transpose(1, 2).reshape(qkv.shape[0], -1).to(
+        qkv.dtype)
+
+
+def _field_attention_ref_bwd(grad_out: torch.Tensor, qkv: torch.Tensor,
+                             n_fields: int, n_heads: int,
+                             scale: float) -> torch.Tensor:
+    """``dqkv`` of the composition by the definition's formulas: ``dS`` and
+    ``delta`` from the cast attention matrix, ``dS`` cast once."""
+    q, k, v, pb = _field_attention_parts(qkv, n_fields, n_heads, scale)
+    g = grad_out.reshape(-1, n_fields, n_heads, q.shape[-1]).float() \
+        .transpose(1, 2)
+    dp = g.matmul(v.transpose(-1, -2))
+    delta = (pb * dp).sum(-1, keepdim=True)
+    ds = (scale * pb * (dp - delta)).to(qkv.dtype).float()
+    parts = (ds.matmul(k), ds.transpose(-1, -2).matmul(q),
+             pb.transpose(-1, -2).matmul(g))
+    return torch.stack(parts, dim=2).permute(0, 3, 2, 1, 4).reshape(
+        qkv.shape).to(qkv.dtype)
+
+
+class FieldAttentionFn(torch.autograd.Function):
+    """``out [B*N, H*d] = field_attention(qkv [B*N, 3*H*d])``
+    (docs/Kernels.md, "Field attention"): softmax attention among the ``N``
+    tokens of each example, per head.  Where
+    :func:`field_attention_kernel_ok` holds, forward and backward are one
+    HIP kernel each and the backward returns one packed ``dqkv``; every
+    other case (the CPU, fp32, shapes and layouts the kernels refuse,
+    ``MIYARN_FIELD_ATTENTION=0``) is the torch composition."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_fields, n_heads, scale, max_blocks):
+        ctx.kernel = field_attention_kernel_ok(qkv, n_fields, n_heads)
+        ctx.args = (n_fields, n_heads, scale, max_blocks)
+        ctx.save_for_backward(qkv)
+        if ctx.kernel:
+            return _C.field_attention_fwd(qkv, n_fields, n_heads, scale,
+                                          max_blocks)
+        if _on_gpu(qkv):
+            _require_ext()
+        return _field_attention_ref(qkv, n_fields, n_heads, scale)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, = ctx.saved_tensors
+        n_fields, n_heads, scale, max_blocks = ctx.args
+        if ctx.kernel:
+            # what the binding would refuse (the expanded grad of a sum
+            # over the rows, an odd offset) is copied; clone, not
+            # contiguous(): dense rows at an odd offset ARE contiguous
+            if not _C.field_attention_rows_ok(grad_out):
+                grad_out = grad_out.clone(
+                    memory_format=torch.contiguous_format)
+            return (_C.field_attention_bwd(grad_out, qkv, n_fields, n_heads,
+                                           scale, max_blocks),
+                    None, None, None, None)
+        return (_field_attention_ref_bwd(grad_out, qkv, n_fields, n_heads,
+                                         scale), None, None, None, None)
+
+
+def field_attention(qkv: torch.Tensor, n_fields: int, n_heads: int,
+                    scale: Optional[float] = None,
+                    max_blocks: int = 0) -> torch.Tensor:
+    """Multi-head self-attention over each example's ``n_fields`` tokens
+    (:class:`FieldAttentionFn`).  Row ``b*N + i`` of ``qkv`` is token ``i``
+    of example ``b`` as ``[q | k | v]``, each ``H*d`` wide with head ``h`` at
+    columns ``h*d .. h*d + d - 1``: what one linear layer over the tokens
+    writes.  ``scale`` defaults to ``d ** -0.5``; ``max_blocks`` caps the
+    kernels' grid (0: the normal cap)."""
+    if scale is None:
+        scale = (qkv.shape[1] // (3 * n_heads)) ** -0.5
+    return FieldAttentionFn.apply(qkv, n_fields, n_heads, float(scale),
+                                  max_blocks)
+
+
 def fused_head_bwd_enabled() -> bool:
     """MIYARN_FUSED_HEAD_BWD=0 restores the separate last layer and head
     (the head's backward materialises its ``[B, width]`` input gradient)."""

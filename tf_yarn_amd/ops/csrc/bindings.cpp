@@ -179,6 +179,16 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> cross_fwd(
 std::vector<torch::Tensor> cross_bwd_pre(torch::Tensor g, torch::Tensor x0,
                                          torch::Tensor v);
 
+// field_attention.hip
+bool field_attention_ok(torch::Tensor qkv, int64_t n_fields, int64_t n_heads);
+bool field_attention_rows_ok(torch::Tensor grad_out);
+torch::Tensor field_attention_fwd(torch::Tensor qkv, int64_t n_fields,
+                                  int64_t n_heads, double scale,
+                                  int64_t max_blocks);
+torch::Tensor field_attention_bwd(torch::Tensor grad_out, torch::Tensor qkv,
+                                  int64_t n_fields, int64_t n_heads,
+                                  double scale, int64_t max_blocks);
+
 // eval_metrics.hip
 void binary_eval_update(torch::Tensor logits, torch::Tensor labels,
                         torch::Tensor hist, torch::Tensor counts,
@@ -328,6 +338,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "below and its dbias in the epilogue (returns [dz, dbias])",
         py::arg("dz_next"), py::arg("w"), py::arg("y"),
         py::arg("dbias_bf16") = false);
+  m.def("field_attention_ok", &field_attention_ok,
+        "True when the field-attention kernels take these operands",
+        py::arg("qkv"), py::arg("n_fields"), py::arg("n_heads"));
+  m.def("field_attention_rows_ok", &field_attention_rows_ok,
+        "True when field_attention_bwd reads this grad_out in place",
+        py::arg("grad_out"));
+  m.def("field_attention_fwd", &field_attention_fwd,
+        "Multi-head self-attention over each example's n_fields tokens, "
+        "qkv [B*N, 3*H*d] -> out [B*N, H*d], in one MFMA kernel; max_blocks "
+        "caps the grid (0: the normal cap)",
+        py::arg("qkv"), py::arg("n_fields"), py::arg("n_heads"),
+        py::arg("scale"), py::arg("max_blocks") = 0);
+  m.def("field_attention_bwd", &field_attention_bwd,
+        "dqkv [B*N, 3*H*d] of field_attention_fwd from qkv and grad_out in "
+        "one kernel (the attention matrix is recomputed)",
+        py::arg("grad_out"), py::arg("qkv"), py::arg("n_fields"),
+        py::arg("n_heads"), py::arg("scale"), py::arg("max_blocks") = 0);
   m.def("cross_layer_ok", &cross_layer_ok,
         "True when the cross-layer kernels take these operands",
         py::arg("x0"), py::arg("x"), py::arg("weight"), py::arg("bias"));
