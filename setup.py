@@ -42,6 +42,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "dgrad_drelu.hip"),
         os.path.join(CSRC, "cross_layer.hip"),
         os.path.join(CSRC, "field_attention.hip"),
+        os.path.join(CSRC, "cin_layer.hip"),
         os.path.join(CSRC, "lt_linear.hip"),
         os.path.join(CSRC, "eval_metrics.hip"),
     ],

@@ -1972,6 +1972,130 @@ def field_attention(qkv: torch.Tensor, n_fields: int, n_heads: int,
                                   max_blocks)
 
 
+# ---- CIN layer (xDeepFM) ---------------------------------------------------
+
+def cin_layer_enabled() -> bool:
+    """MIYARN_CIN_LAYER=0 sends bf16 GPU operands through the torch
+    composition too."""
+    return _env_switch_on("MIYARN_CIN_LAYER")
+
+
+def _cin_layer_dims(x0, x, weight, n_fields):
+    """``(B, D, H_in, H_out)`` of a well-formed call."""
+    if (x0.dim() != 2 or x.dim() != 2 or weight.dim() != 3 or n_fields < 1
+            or weight.shape[2] != n_fields or x0.shape[1] % n_fields
+            or x.shape[0] != x0.shape[0]
+            or x.shape[1] != weight.shape[1] * (x0.shape[1] // n_fields)):
+        raise ValueError(
+            f"x0 {tuple(x0.shape)}, x {tuple(x.shape)} and weight "
+            f"{tuple(weight.shape)} are not [B, {n_fields}*D], [B, H_in*D] "
+            f"and [H_out, H_in, {n_fields}]")
+    return (x0.shape[0], x0.shape[1] // n_fields, weight.shape[1],
+            weight.shape[0])
+
+
+def cin_layer_kernel_ok(x0: torch.Tensor, x: torch.Tensor,
+                        weight: torch.Tensor, n_fields: int) -> bool:
+    """True when :func:`cin_layer` runs the HIP kernels
+    (``csrc/cin_layer.hip``): bf16 ``x0 [B, m*D]``, ``x [B, H_in*D]`` and a
+    contiguous ``weight [H_out, H_in, m]`` on one GPU, ``D`` in {16, 32, 64},
+    ``2 <= m <= 32``, ``1 <= H_in <= 256``, ``H_out % 16 == 0``,
+    ``16 <= H_out <= 256``, ``x0`` and ``x`` with unit column stride, a row
+    stride that is a multiple of 8 elements and at least the row's width,
+    and a 16-byte aligned base."""
+    return (HAVE_EXT and x0.is_cuda and x.is_cuda and weight.is_cuda
+            and weight.dim() == 3 and weight.shape[2] == n_fields
+            and cin_layer_enabled() and _C.cin_layer_ok(x0, x, weight))
+
+
+def _cin_layer_parts(x0, x, weight, n_fields):
+    """fp32 ``x0 [B, m, D]``, ``x [B, H_in, D]``, ``weight`` and the outer
+    product ``z [B, H_in, m, D]``, rounded ONCE to ``x``'s dtype."""
+    b, d, h_in, _ = _cin_layer_dims(x0, x, weight, n_fields)
+    x0f = x0.float().reshape(b, n_fields, d)
+    xf = x.float().reshape(b, h_in, d)
+    z = (xf.unsqueeze(2) * x0f.unsqueeze(1)).to(x.dtype).float()
+    return x0f, xf, weight.float(), z
+
+
+def _cin_layer_ref(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
+                   n_fields: int) -> torch.Tensor:
+    """The composition: fp32 products, one cast of ``z``, fp32 ``einsum``,
+    one cast."""
+    _, _, wf, z = _cin_layer_parts(x0, x, weight, n_fields)
+    return torch.einsum("hij,bijc->bhc", wf, z).reshape(
+        x0.shape[0], -1).to(x.dtype)
+
+
+def _cin_layer_ref_bwd(grad_y: torch.Tensor, x0: torch.Tensor,
+                       x: torch.Tensor, weight: torch.Tensor, n_fields: int):
+    """``(dx0, dx, dW)`` of the composition by the definition's formulas:
+    the cast of ``z`` is the identity for ``dU`` (fp32, never rounded) and
+    ``dW`` takes the cast ``z``."""
+    x0f, xf, wf, z = _cin_layer_parts(x0, x, weight, n_fields)
+    b = x0.shape[0]
+    g = grad_y.float().reshape(b, weight.shape[0], -1)
+    du = torch.einsum("bhc,hij->bijc", g, wf)
+    dx = (du * x0f.unsqueeze(1)).sum(2).reshape(b, -1)
+    dx0 = (du * xf.unsqueeze(2)).sum(1).reshape(b, -1)
+    dw = torch.einsum("bhc,bijc->hij", g, z)
+    return dx0.to(x0.dtype), dx.to(x.dtype), dw.to(weight.dtype)
+
+
+class CINLayerFn(torch.autograd.Function):
+    """``y[b,h,c] = sum_ij W[h,i,j] * bf16(x[b,i,c] * x0[b,j,c])``
+    (docs/Kernels.md, "CIN layer").  Where :func:`cin_layer_kernel_ok`
+    holds, the forward, the data gradients and the weight gradient are one
+    MFMA kernel each and the ``[B, H_in*m, D]`` outer product is never
+    formed; every other case (the CPU, fp32, shapes and layouts the kernels
+    refuse, ``MIYARN_CIN_LAYER=0``) is the torch composition."""
+
+    @staticmethod
+    def forward(ctx, x0, x, weight, n_fields, max_blocks):
+        _cin_layer_dims(x0, x, weight, n_fields)
+        ctx.kernel = cin_layer_kernel_ok(x0, x, weight, n_fields)
+        ctx.args = (n_fields, max_blocks)
+        ctx.save_for_backward(x0, x, weight)
+        if ctx.kernel:
+            return _C.cin_layer_fwd(x0, x, weight, max_blocks)
+        if _on_gpu(x0, x, weight):
+            _require_ext()
+        return _cin_layer_ref(x0, x, weight, n_fields)
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x0, x, weight = ctx.saved_tensors
+        n_fields, max_blocks = ctx.args
+        if not ctx.kernel:
+            return (*_cin_layer_ref_bwd(grad_y, x0, x, weight, n_fields),
+                    None, None)
+        # what the bindings would refuse (the expanded grad of a pooled
+        # sum, an odd offset) is copied; clone, not contiguous(): dense
+        # rows at an odd offset ARE contiguous
+        if not _C.cin_layer_rows_ok(grad_y):
+            grad_y = grad_y.clone(memory_format=torch.contiguous_format)
+        dx0 = dx = dw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dx, dx0 = _C.cin_layer_bwd_data(grad_y, x0, x, weight,
+                                            max_blocks)
+        if ctx.needs_input_grad[2]:
+            dw = _C.cin_layer_bwd_weight(grad_y, x0, x, weight, max_blocks)
+        return dx0, dx, dw, None, None
+
+
+def cin_layer(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
+              n_fields: int, max_blocks: Optional[int] = None
+              ) -> torch.Tensor:
+    """One Compressed Interaction Network layer of xDeepFM
+    (:class:`CINLayerFn`): ``x0 [B, m*D]`` holds field ``j`` of an example
+    at columns ``j*D .. j*D + D - 1``, ``x [B, H_in*D]`` the previous
+    layer's maps (``x0`` itself for the first layer, ``H_in = m``),
+    ``weight [H_out, H_in, m]``; returns ``y [B, H_out*D]``.  No bias, no
+    activation.  ``max_blocks`` caps the kernels' grids and the weight
+    gradient's batch splits (``None`` or 0: the normal caps)."""
+    return CINLayerFn.apply(x0, x, weight, n_fields, max_blocks or 0)
+
+
 def fused_head_bwd_enabled() -> bool:
     """MIYARN_FUSED_HEAD_BWD=0 restores the separate last layer and head
     (the head's backward materialises its ``[B, width]`` input gradient)."""

@@ -189,6 +189,20 @@ torch::Tensor field_attention_bwd(torch::Tensor grad_out, torch::Tensor qkv,
                                   int64_t n_fields, int64_t n_heads,
                                   double scale, int64_t max_blocks);
 
+// cin_layer.hip
+bool cin_layer_ok(torch::Tensor x0, torch::Tensor x, torch::Tensor weight);
+bool cin_layer_rows_ok(torch::Tensor grad_y);
+torch::Tensor cin_layer_fwd(torch::Tensor x0, torch::Tensor x,
+                            torch::Tensor weight, int64_t max_blocks);
+std::vector<torch::Tensor> cin_layer_bwd_data(torch::Tensor grad_y,
+                                              torch::Tensor x0,
+                                              torch::Tensor x,
+                                              torch::Tensor weight,
+                                              int64_t max_blocks);
+torch::Tensor cin_layer_bwd_weight(torch::Tensor grad_y, torch::Tensor x0,
+                                   torch::Tensor x, torch::Tensor weight,
+                                   int64_t max_blocks);
+
 // eval_metrics.hip
 void binary_eval_update(torch::Tensor logits, torch::Tensor labels,
                         torch::Tensor hist, torch::Tensor counts,
@@ -370,6 +384,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Elementwise front of the cross layer's backward in one pass; "
         "returns (dz = g * x0, dx0 = g * v, dbias = column sums of dz)",
         py::arg("g"), py::arg("x0"), py::arg("v"));
+  m.def("cin_layer_ok", &cin_layer_ok,
+        "True when the CIN-layer kernels take these operands",
+        py::arg("x0"), py::arg("x"), py::arg("weight"));
+  m.def("cin_layer_rows_ok", &cin_layer_rows_ok,
+        "True when the CIN-layer backward kernels read this grad_y in place",
+        py::arg("grad_y"));
+  m.def("cin_layer_fwd", &cin_layer_fwd,
+        "CIN layer y[b,h,c] = sum_ij W[h,i,j] bf16(x[b,i,c] x0[b,j,c]) in "
+        "one MFMA kernel, x0 [B, m*D], x [B, H_in*D], weight [H_out, H_in, "
+        "m] -> y [B, H_out*D]; max_blocks caps the grid (0: the normal cap)",
+        py::arg("x0"), py::arg("x"), py::arg("weight"),
+        py::arg("max_blocks") = 0);
+  m.def("cin_layer_bwd_data", &cin_layer_bwd_data,
+        "(dx, dx0) of cin_layer_fwd in one kernel; dU never reaches memory",
+        py::arg("grad_y"), py::arg("x0"), py::arg("x"), py::arg("weight"),
+        py::arg("max_blocks") = 0);
+  m.def("cin_layer_bwd_weight", &cin_layer_bwd_weight,
+        "dW of cin_layer_fwd: per-split fp32 partials summed in split order "
+        "(deterministic); max_blocks also caps the splits",
+        py::arg("grad_y"), py::arg("x0"), py::arg("x"), py::arg("weight"),
+        py::arg("max_blocks") = 0);
   m.def("binary_eval_update", &binary_eval_update,
         "Fold a batch of (logit, label) into the streaming binary eval "
         "state: score histogram [2, 4096], counts (n_valid, n_nan, tp, fp), "
