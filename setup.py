@@ -41,6 +41,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "gemm_bt.hip"),
         os.path.join(CSRC, "dgrad_drelu.hip"),
         os.path.join(CSRC, "cross_layer.hip"),
+        os.path.join(CSRC, "cross_lowrank.hip"),
         os.path.join(CSRC, "field_attention.hip"),
         os.path.join(CSRC, "cin_layer.hip"),
         os.path.join(CSRC, "lt_linear.hip"),

@@ -6,7 +6,8 @@ the way :class:`WideAndDeep` builds its deep input (``_DeepInput`` one-hot,
 ``ops.EmbeddingBagFn`` writing behind the dense columns multi-hot), then
 ``n_cross`` cross layers ``x <- x0 * (x @ W^T + b) + x``
 (:func:`tf_yarn_amd.ops.cross_layer`: one MFMA kernel forward in bf16 on
-the GPU), an MLP of Linear + ReLU and a single-logit head.  The tables are
+the GPU; with ``cross_rank`` the low-rank ``W = U V^T`` of
+:func:`tf_yarn_amd.ops.cross_layer_lowrank`), an MLP of Linear + ReLU and a single-logit head.  The tables are
 replicated; every sparse rule and the multi-hot bags of
 :class:`SparseEmbedding` apply unchanged, and the sparse sync methods have
 :class:`WideAndDeep`'s signatures, so the same training loops drive it.
@@ -43,13 +44,36 @@ class CrossLayer(nn.Module):
         return ops.cross_layer(x0, x, self.weight, self.bias)
 
 
-class CrossNetwork(nn.Module):
-    """``n_layers`` cross layers, starting from ``x = x0``."""
+class LowRankCrossLayer(nn.Module):
+    """``forward(x0, x) = x0 * (u_weight @ (v_weight @ x) + bias) + x``: the
+    low-rank cross layer with ``v_weight [rank, dim]`` (down) and
+    ``u_weight [dim, rank]`` (up), both initialised like
+    :class:`CrossLayer`'s weight, and a zero ``bias``."""
 
-    def __init__(self, dim: int, n_layers: int, dtype=torch.float32):
+    def __init__(self, dim: int, rank: int, dtype=torch.float32):
+        super().__init__()
+        self.v_weight = nn.Parameter(torch.empty(rank, dim, dtype=dtype))
+        self.u_weight = nn.Parameter(torch.empty(dim, rank, dtype=dtype))
+        self.bias = nn.Parameter(torch.zeros(dim, dtype=dtype))
+        nn.init.kaiming_uniform_(self.v_weight, a=math.sqrt(5))
+        nn.init.kaiming_uniform_(self.u_weight, a=math.sqrt(5))
+
+    def forward(self, x0: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        return ops.cross_layer_lowrank(x0, x, self.v_weight, self.u_weight,
+                                       self.bias)
+
+
+class CrossNetwork(nn.Module):
+    """``n_layers`` cross layers, starting from ``x = x0``: full-rank
+    :class:`CrossLayer` s, or :class:`LowRankCrossLayer` s of ``rank``."""
+
+    def __init__(self, dim: int, n_layers: int, dtype=torch.float32,
+                 rank: Optional[int] = None):
         super().__init__()
         self.layers = nn.ModuleList(
-            CrossLayer(dim, dtype) for _ in range(n_layers))
+            CrossLayer(dim, dtype) if rank is None
+            else LowRankCrossLayer(dim, rank, dtype)
+            for _ in range(n_layers))
 
     def forward(self, x0: torch.Tensor) -> torch.Tensor:
         x = x0
@@ -73,9 +97,12 @@ class DCN(nn.Module):
                  sparse_eps: float = 1e-10,
                  sparse_initial_accumulator: float = 0.0,
                  sparse_l1: float = 0.0, sparse_l2: float = 0.0,
-                 sparse_betas: Tuple[float, float] = (0.9, 0.999)):
+                 sparse_betas: Tuple[float, float] = (0.9, 0.999),
+                 cross_rank: Optional[int] = None):
         """``n_cross``: the number of cross layers over the
         ``16 + len(table_sizes) * embedding_dim`` columns of ``x0``;
+        ``cross_rank``: ``None`` for full-rank layers, else the rank of
+        :class:`LowRankCrossLayer` (about a quarter of the columns);
         ``deep``: the widths of the MLP behind them, which feeds the
         single-logit head.  ``dense_dim`` is at most 16 (the dense columns
         share ``WideAndDeep``'s 16-column slot of the input buffer).  The
@@ -97,7 +124,7 @@ class DCN(nn.Module):
             sparse_l1=sparse_l1, sparse_l2=sparse_l2,
             sparse_betas=sparse_betas)
         dim = _DeepInput.DENSE_PAD + len(table_sizes) * embedding_dim
-        self.cross = CrossNetwork(dim, n_cross)
+        self.cross = CrossNetwork(dim, n_cross, rank=cross_rank)
         self.mlp, width = _mlp(dim, deep)
         self.head = ScalarHead(width, compute_dtype)
         if bf16:

@@ -1858,6 +1858,93 @@ def cross_layer(x0: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,
     return CrossLayerFn.apply(x0, x, weight, bias, save_v)
 
 
+# ---- low-rank cross layer (DCN-v2) -----------------------------------------
+
+def cross_layer_lowrank_kernel_ok(x0: torch.Tensor, x: torch.Tensor,
+                                  v_weight: torch.Tensor,
+                                  u_weight: torch.Tensor,
+                                  bias: torch.Tensor) -> bool:
+    """True when :func:`cross_layer_lowrank` runs the HIP kernels
+    (``csrc/cross_lowrank.hip``): all bf16 on one GPU, ``D % 16 == 0``,
+    ``16 <= D <= 1024``, ``r % 16 == 0``, ``16 <= r <= 128``, ``v_weight
+    [r, D]``, ``u_weight [D, r]`` and ``bias [D]`` contiguous, ``x0`` and
+    ``x`` as :func:`cross_layer_kernel_ok` wants them, and
+    ``MIYARN_CROSS_LAYER`` (shared with :func:`cross_layer`) not ``0``."""
+    tensors = (x0, x, v_weight, u_weight, bias)
+    return (HAVE_EXT and all(t.is_cuda for t in tensors)
+            and _cross_layer_mode() != "off"
+            and _C.cross_lowrank_ok(*tensors))
+
+
+def _cross_layer_lowrank_ref(x0: torch.Tensor, x: torch.Tensor,
+                             v_weight: torch.Tensor, u_weight: torch.Tensor,
+                             bias: torch.Tensor) -> torch.Tensor:
+    """The composition: both products in fp32 with ``t`` cast to ``x``'s
+    dtype between them (the kernel's one intermediate rounding), the bias,
+    the multiply and the add in fp32, one final cast."""
+    xf = x.float()
+    t = xf.matmul(v_weight.float().t()).to(x.dtype)
+    v = t.float().matmul(u_weight.float().t()) + bias.float()
+    return (x0.float() * v + xf).to(x.dtype)
+
+
+class CrossLayerLowRankFn(torch.autograd.Function):
+    """``y = x0 * (t @ u_weight.T + bias) + x`` with ``t = x @ v_weight.T``
+    rounded to bf16 (docs/Kernels.md, "Low-rank cross layer").  Where
+    :func:`cross_layer_lowrank_kernel_ok` holds the forward is one chained
+    MFMA kernel (``_C.cross_lowrank_fwd``: ``t`` stays on chip between the
+    two GEMMs) and the backward ``_C.cross_bwd_pre``, the same chain with
+    the weights transposed (``_C.cross_lowrank_bwd_dx``: ``dt`` and ``dx``)
+    and two weight gradients on the linear layers' path; every other case
+    is the torch composition."""
+
+    @staticmethod
+    def forward(ctx, x0, x, v_weight, u_weight, bias, save):
+        ctx.kernel = cross_layer_lowrank_kernel_ok(x0, x, v_weight, u_weight,
+                                                   bias)
+        if ctx.kernel:
+            y, t, v = _C.cross_lowrank_fwd(x0, x, v_weight, u_weight, bias,
+                                           save)
+            ctx.save_for_backward(x0, x, v_weight, u_weight, t, v)
+            return y
+        if _on_gpu(x0, x, v_weight, u_weight, bias):
+            _require_ext()
+        ctx.save_for_backward(x0, x, v_weight, u_weight, bias)
+        return _cross_layer_lowrank_ref(x0, x, v_weight, u_weight, bias)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kernel:
+            x0, x, v_weight, u_weight, t, v = ctx.saved_tensors
+            if not _C.cross_rows_ok(g):  # as CrossLayerFn.backward
+                g = g.clone(memory_format=torch.contiguous_format)
+            dz, dx0, dbias = _C.cross_bwd_pre(g, x0, v)
+            # the chain wants both weights K-major: two small transposed
+            # copies per backward (at most 1024 x 128 elements each)
+            dx, dt = _C.cross_lowrank_bwd_dx(
+                dz, g, u_weight.t().contiguous(), v_weight.t().contiguous())
+            return (dx0, dx, _linear_wgrad(dt, x, v_weight),
+                    _linear_wgrad(dz, t, u_weight), dbias, None)
+        x0, x, v_weight, u_weight, bias = ctx.saved_tensors
+        with torch.enable_grad():
+            leaves = [p.detach().requires_grad_()
+                      for p in (x0, x, v_weight, u_weight, bias)]
+            y = _cross_layer_lowrank_ref(*leaves)
+        return (*torch.autograd.grad(y, leaves, g), None)
+
+
+def cross_layer_lowrank(x0: torch.Tensor, x: torch.Tensor,
+                        v_weight: torch.Tensor, u_weight: torch.Tensor,
+                        bias: torch.Tensor) -> torch.Tensor:
+    """One low-rank DCN-v2 cross layer, ``x0 * (u_weight @ (v_weight @ x) +
+    bias) + x`` with ``v_weight [r, D]`` and ``u_weight [D, r]``
+    (:class:`CrossLayerLowRankFn`).  The kernel writes ``t`` and ``v`` for
+    the backward only if some input needs a gradient."""
+    save = torch.is_grad_enabled() and any(
+        p.requires_grad for p in (x0, x, v_weight, u_weight, bias))
+    return CrossLayerLowRankFn.apply(x0, x, v_weight, u_weight, bias, save)
+
+
 # ---- field self-attention (AutoInt) ----------------------------------------
 
 def field_attention_enabled() -> bool:

@@ -179,6 +179,19 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> cross_fwd(
 std::vector<torch::Tensor> cross_bwd_pre(torch::Tensor g, torch::Tensor x0,
                                          torch::Tensor v);
 
+// cross_lowrank.hip
+bool cross_lowrank_ok(torch::Tensor x0, torch::Tensor x,
+                      torch::Tensor v_weight, torch::Tensor u_weight,
+                      torch::Tensor bias);
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>>
+cross_lowrank_fwd(torch::Tensor x0, torch::Tensor x, torch::Tensor v_weight,
+                  torch::Tensor u_weight, torch::Tensor bias, bool save);
+std::vector<torch::Tensor> cross_lowrank_bwd_dx(torch::Tensor dz,
+                                                torch::Tensor g,
+                                                torch::Tensor ut,
+                                                torch::Tensor vt);
+
 // field_attention.hip
 bool field_attention_ok(torch::Tensor qkv, int64_t n_fields, int64_t n_heads);
 bool field_attention_rows_ok(torch::Tensor grad_out);
@@ -384,6 +397,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Elementwise front of the cross layer's backward in one pass; "
         "returns (dz = g * x0, dx0 = g * v, dbias = column sums of dz)",
         py::arg("g"), py::arg("x0"), py::arg("v"));
+  m.def("cross_lowrank_ok", &cross_lowrank_ok,
+        "True when the low-rank cross-layer kernels take these operands",
+        py::arg("x0"), py::arg("x"), py::arg("v_weight"),
+        py::arg("u_weight"), py::arg("bias"));
+  m.def("cross_lowrank_fwd", &cross_lowrank_fwd,
+        "Low-rank cross layer y = x0 * (U bf16(V x) + b) + x in one chained "
+        "MFMA kernel, v_weight [r, D], u_weight [D, r]; returns (y, t, v) "
+        "with t = bf16(x @ V^T) and v = bf16(t @ U^T + b) when save, else "
+        "(y, None, None)",
+        py::arg("x0"), py::arg("x"), py::arg("v_weight"),
+        py::arg("u_weight"), py::arg("bias"), py::arg("save"));
+  m.def("cross_lowrank_bwd_dx", &cross_lowrank_bwd_dx,
+        "Data gradient of the low-rank cross layer in one chained MFMA "
+        "kernel from contiguous ut = U^T [r, D] and vt = V^T [D, r]; returns "
+        "(dx = bf16(dt @ V + g), dt = bf16(dz @ U))",
+        py::arg("dz"), py::arg("g"), py::arg("ut"), py::arg("vt"));
   m.def("cin_layer_ok", &cin_layer_ok,
         "True when the CIN-layer kernels take these operands",
         py::arg("x0"), py::arg("x"), py::arg("weight"));
