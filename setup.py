@@ -38,6 +38,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "sparse_adagrad.hip"),
         os.path.join(CSRC, "elementwise.hip"),
         os.path.join(CSRC, "wgrad.hip"),
+        os.path.join(CSRC, "wgrad_narrow.hip"),
         os.path.join(CSRC, "gemm_bt.hip"),
         os.path.join(CSRC, "dgrad_drelu.hip"),
         os.path.join(CSRC, "cross_layer.hip"),

@@ -1737,13 +1737,41 @@ def _linear_bias_relu_fwd(x: torch.Tensor, weight: torch.Tensor,
     return bias_relu_fwd(x.matmul(weight.t()), bias)
 
 
+def _narrow_wgrad_ok(dz: torch.Tensor, x: torch.Tensor) -> bool:
+    """Whether ``_C.wgrad_narrow`` takes ``dz.T @ x``: one side of the
+    output 8..128 wide, the other at most 1024, both multiples of 8, any
+    batch >= 1 (the low-rank cross layer's ``dU`` and ``dV``, a projection
+    to a small width, a ragged batch of such a layer).  Asked only after
+    :func:`_custom_wgrad_kernel` returned ``None``; ``MIYARN_WGRAD=lib``
+    switches it off with that one.  docs/Kernels.md ("Narrow weight
+    gradient") has the measurement behind the default."""
+    if os.environ.get("MIYARN_WGRAD") == "lib":
+        return False
+    if not (HAVE_EXT and dz.is_cuda and x.is_cuda):
+        return False
+    if dz.dtype != torch.bfloat16 or x.dtype != torch.bfloat16:
+        return False
+    if dz.dim() != 2 or x.dim() != 2 or x.size(0) != dz.size(0) \
+            or dz.size(0) < 1:
+        return False
+    if not (dz.is_contiguous() and x.is_contiguous()) \
+            or dz.data_ptr() % 16 or x.data_ptr() % 16:
+        return False
+    r, wide = sorted((dz.size(1), x.size(1)))
+    return r % 8 == 0 and 8 <= r <= 128 and wide % 8 == 0 and wide <= 1024
+
+
 def _linear_wgrad(dz: torch.Tensor, x: torch.Tensor,
                   weight: torch.Tensor) -> torch.Tensor:
     """``dz.T @ x`` in ``weight``'s dtype: the custom split-K kernel where
     :func:`_custom_wgrad_kernel` picks one (split-K partial sum + cast
-    fused into one reduce kernel), else the library."""
+    fused into one reduce kernel), else the narrow-output kernel where
+    :func:`_narrow_wgrad_ok` admits the shape, else the library."""
     kernel = _custom_wgrad_kernel(dz, x)
     if kernel is None:
+        if _narrow_wgrad_ok(dz, x):
+            dw = _C.wgrad_narrow(dz, x, 0, weight.dtype == torch.bfloat16)
+            return dw if dw.dtype == weight.dtype else dw.to(weight.dtype)
         return dz.t().matmul(x)
     regstage = True if os.environ.get("MIYARN_WGRAD") == "regstage" else None
     dw = kernel(dz, x, 0, weight.dtype == torch.bfloat16, regstage)

@@ -159,6 +159,11 @@ torch::Tensor wgrad_nt256(torch::Tensor dy, torch::Tensor x,
                           int64_t splitk, bool out_bf16,
                           c10::optional<bool> regstage);
 py::dict wgrad_glds_layout();
+
+// wgrad_narrow.hip
+torch::Tensor wgrad_narrow(torch::Tensor dy, torch::Tensor x, int64_t splitk,
+                           bool out_bf16);
+
 void convert_scaled(torch::Tensor src, torch::Tensor dst, double scale);
 
 // gemm_bt.hip
@@ -317,6 +322,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_bf16") = false, py::arg("regstage") = py::none());
   m.def("wgrad_glds_layout", &wgrad_glds_layout,
         "Constants and image table of the wgrad kernels' LDS-DMA staging");
+  m.def("wgrad_narrow", &wgrad_narrow,
+        "Split-K MFMA weight gradient dW = dy^T @ x (bf16 in) for a narrow "
+        "side: min(N, M) % 8 == 0 in [8, 128], max(N, M) % 8 == 0 up to "
+        "1024, any B >= 1; splitk = 0 picks the plan",
+        py::arg("dy"), py::arg("x"), py::arg("splitk") = 0,
+        py::arg("out_bf16") = false);
   m.def("col_reduce_dot", &col_reduce_dot,
         "dw[m] = sum_b dy[b] * x[b,m] (single-logit head wgrad)");
   m.def("col_reduce_dot_sum", &col_reduce_dot_sum,
